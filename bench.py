@@ -8,6 +8,8 @@ configs[2]), on N GPUs of one node.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --config e2e          # BASELINE configs[4] shape: audio -> embedder -> APA + FAD (see run_e2e)
+    python bench.py --gpus 1 --steps 5 --warmup 1 --full                  # everything else the bench measures or checks
+    python bench.py --gpus 1 --steps 5 --warmup 1 --dump-outputs DIR      # + the last timed step's results as DIR/<key>.npy
 
 A step is one COLD evaluation: both sets' statistics, the Frechet distance, the
 100 x 1000 kernel-distance subsets, both sets' k-NN radii and the membership
@@ -17,13 +19,14 @@ the stats / gathered embeddings / radii / counts go through RCCL collectives.
 Rank 0 prints ONE JSON line.
 
 Inputs come from numpy's PCG64 (tests/golden/inputs.py: bench_pair), so the CPU oracle can reproduce them:
-tests/golden/bench_prdc.npz holds oracle.prdc_blocked's values for exactly these sets and the line's `result` is
-checked against it (`result_check`).
+tests/golden/bench_prdc.npz holds oracle.prdc_blocked's values for exactly these sets and, with --full, the line's
+`result` is checked against it (`result_check`).
 
-Beside the contract's keys the line carries `roofline` / `other_tile_kernel` / `cpu_baseline`, `variants`, `filter`, `warm`,
-`first_call`, and (round 6) `process_cold` - with one GPU: ONE evaluate() of a fresh process, started as a child before this
-process touches the GPU (--no-process-cold skips it) - and, with several ranks, `c_entry_ms` beside `python_schedule_ms`: both
-exchange schedules timed back to back (the one the flags chose is `value`).
+A plain run sets up, warms up, times the K steps, writes --dump-outputs if asked and prints the line: the contract's keys,
+`config` and `result`.  With --full the line also carries `result_check`, `roofline` / `other_tile_kernel` / `cpu_baseline`,
+`variants`, `filter`, `warm`, `first_call`, and `process_cold` - with one GPU: ONE evaluate() of a fresh process, started as a
+child before this process touches the GPU (--no-process-cold skips it) - and, with several ranks, `c_entry_ms` beside
+`python_schedule_ms`: both exchange schedules timed back to back (the one the flags chose is `value`).
 """
 import argparse
 import json
@@ -328,6 +331,14 @@ def process_cold(argv_tail):
     return {"error": "no record", "returncode": r.returncode, "stderr_tail": r.stderr[-400:]}
 
 
+def dump_outputs(directory, result):
+    """--dump-outputs: what the timed path handed its caller in its last timed step - the evaluate() dict of floats - as one
+    float64 array per key (DIR/<key>.npy), so that two builds can be compared output for output on the same seeded inputs."""
+    os.makedirs(directory, exist_ok=True)
+    for key, value in result.items():
+        np.save(os.path.join(directory, key + ".npy"), np.asarray(value, dtype=np.float64))
+
+
 def timed_steps(step, fence, steps, warmup):
     for _ in range(warmup):
         result = step()
@@ -350,9 +361,14 @@ def main():
     ap.add_argument("--nearest-k", type=int, default=5)
     ap.add_argument("--data", choices=("randn", "clap"), default="randn",
                     help="randn: SURVEY 8(d) C3 sets; clap: unit-norm rows with offsets 0.5 / 0.55 (CLAP-shaped)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-variants", action="store_true")
-    ap.add_argument("--no-process-cold", action="store_true", help="skip the fresh-process time-to-first-result child")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: the fixture check, the per-kernel / roofline pass, the variants, the warm, "
+                         "first-call and fresh-process figures, the CPU baseline and (several ranks) the other exchange schedule")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results to DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-variants", action="store_true", help="--full without the variants")
+    ap.add_argument("--no-process-cold", action="store_true", help="--full without the fresh-process time-to-first-result child")
     ap.add_argument("--process-cold-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--pairs", type=int, default=2000, help="--config e2e: audio pairs per side")
     ap.add_argument("--c-entry", action="store_true",
@@ -361,6 +377,8 @@ def main():
     ap.add_argument("--bulk-communicator", action="store_true",
                     help="row gathers on a second RCCL communicator (distributed.enable_bulk_communicator; default: one)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.process_cold_child:
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
         process_cold_child(args)
@@ -369,7 +387,8 @@ def main():
     # (never under a profiler: its preloaded library has initialised the GPU in THIS process already, and starting another
     # program from a process that holds the GPU is what this pool forbids)
     profiled = any(key.startswith(("ROCPROF", "ROCP_", "ROCTRACER")) for key in os.environ) or "rocprof" in os.environ.get("LD_PRELOAD", "")
-    if args.gpus == 1 and args.config == "evaluate" and not args.no_process_cold and "WORLD_SIZE" not in os.environ and not profiled:
+    if (args.full and args.gpus == 1 and args.config == "evaluate" and not args.no_process_cold and "WORLD_SIZE" not in os.environ
+            and not profiled):
         # a fresh process's ONE evaluate(), measured in a child BEFORE this process initialises the GPU (the child has the device
         # to itself; a child, never an exec)
         cold = process_cold(["--rows", str(args.rows), "--dim", str(args.dim), "--nearest-k", str(args.nearest_k)])
@@ -461,6 +480,16 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    line = headline(args, gi, world, n_ranks_seen, n, d, k, elapsed, result)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, result)
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     # ---- with several ranks: the OTHER schedule timed the same way, so that one driver run says which is faster
     # (VERDICT r5 next-5b): `value` stays the schedule the flags chose, the line carries both as python_schedule_ms / c_entry_ms
     other_schedule_ms = other_schedule_note = None
@@ -700,44 +729,8 @@ def main():
                     "what": ("timed step (one am_evaluate_f32 call + one read-back when n_gpus = 1) against the summed GPU time of "
                              "the main-stream entry points of the same chain; unfused_ms_per_step = the chain issued entry by "
                              "entry from Python with its three read-backs, untimed pass")}
-        out = {
-            "metric": METRIC,
-            "value": args.steps * 2 * n / elapsed,
-            "unit": "embeddings/s",
-            "n_gpus": world,
-            "n_ranks_seen": n_ranks_seen,
-            "library_sources_sha256": library_stamp(),
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic",
-            "config": {"workload": f"FAD+KD+PRDC(k={k}) cold evaluate() of 2x{n} CLAP-{d} f32 embedding sets resident in HBM "
-                                   "(BASELINE.json configs[2])",
-                       "n_ref": n, "n_cand": n, "dim": d, "nearest_k": k, "kd_subsets": 100, "kd_subset_size": 1000,
-                       "inputs": ("numpy PCG64 seed %d: reference randn, candidate randn*1.05+0.05" % gi.BENCH_SEED) if args.data == "randn"
-                                 else ("numpy PCG64 seed %d: unit-norm rows of randn+0.5 / randn+0.55 (CLAP-shaped)" % gi.BENCH_SEED),
-                       "sharding": f"rows/{world}",
-                       "schedule": ("am_evaluate_sharded_f32 (one library call per rank, collectives as hooks)" if args.c_entry and world > 1
-                                    else "am_evaluate_f32 (one library call)" if world == 1
-                                    else "distributed.evaluate_sharded (Python exchange schedule over the split entry points)"),
-                       "arithmetic": "PRDC: results are the exact f32 values (bit-identical to the f32-MFMA kernels); the tile kernels "
-                                     "pre-filter on f16 MFMA with f32 accumulation where am_knn_path/am_prdc_path >= 2 and every "
-                                     "undecided pair is re-evaluated with the exact f32 fmaf chain.  KD (subsets of >= 512 rows, "
-                                     "D >= 128, degree 3): every gathered row is split into two f16 planes (hi = rn16(x), lo = "
-                                     "rn16(x - hi), ~22 significant bits) and the dot products are <hi,hi'> + <lo,hi'> + <hi,lo'> "
-                                     "on the f16 MFMA with f32 accumulation: error of a dot product <= ~3 * 2^-22 |x||y| (one f32 "
-                                     "rounding's worth; the reference forms them in f32 too), kernel values and all sums in f64.  "
-                                     "Statistics: exact f32 products on the f32 MFMA, f64 accumulation.  FAD: f64 throughout.",
-                       "persisting": "between steps nothing of the RESULT is cached (statistics, radii, counts, KD values and the "
-                                     "Frechet solve are recomputed); what survives is allocation and setup: torch's caching "
-                                     "allocator and the evaluate workspace (hip_ops._eval_workspace), the KD subset index table "
-                                     "on the device (a pure function of (n1, n2, S, m, seed): metrics/kd.py device_subset_indices), "
-                                     "code objects and - with several ranks - the communicators.  `first_call` times a step "
-                                     "without them."},
+        out = dict(line)
+        out.update({
             "roofline": main,
             "roofline_step": roofline_step,
             "other_tile_kernel": other,
@@ -751,10 +744,9 @@ def main():
                              "event-to-event time of each C-ABI entry point on its own stream; am_frechet_enqueue_f64 only "
                              "enqueues the solve on a side stream (it runs UNDER the PRDC kernels), so it is left out of the sum"),
             "host_gap": host_gap,
-            "result": result,
             "result_check": check_against_fixture(result, args.data, n, d, k),
             "variants": variants,
-        }
+        })
         if exchange is not None:
             out["exchange"] = exchange
         if other_schedule_note is not None:
@@ -780,6 +772,50 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def headline(args, gi, world, n_ranks_seen, n, d, k, elapsed, result):
+    """The line of a plain run: the contract's keys, the workload and the last timed step's result (--full adds the rest)."""
+    return {
+        "metric": METRIC,
+        "value": args.steps * 2 * n / elapsed,
+        "unit": "embeddings/s",
+        "n_gpus": world,
+        "n_ranks_seen": n_ranks_seen,
+        "library_sources_sha256": library_stamp(),
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic",
+        "config": {"workload": f"FAD+KD+PRDC(k={k}) cold evaluate() of 2x{n} CLAP-{d} f32 embedding sets resident in HBM "
+                               "(BASELINE.json configs[2])",
+                   "n_ref": n, "n_cand": n, "dim": d, "nearest_k": k, "kd_subsets": 100, "kd_subset_size": 1000,
+                   "inputs": ("numpy PCG64 seed %d: reference randn, candidate randn*1.05+0.05" % gi.BENCH_SEED) if args.data == "randn"
+                             else ("numpy PCG64 seed %d: unit-norm rows of randn+0.5 / randn+0.55 (CLAP-shaped)" % gi.BENCH_SEED),
+                   "sharding": f"rows/{world}",
+                   "schedule": ("am_evaluate_sharded_f32 (one library call per rank, collectives as hooks)" if args.c_entry and world > 1
+                                else "am_evaluate_f32 (one library call)" if world == 1
+                                else "distributed.evaluate_sharded (Python exchange schedule over the split entry points)"),
+                   "arithmetic": "PRDC: results are the exact f32 values (bit-identical to the f32-MFMA kernels); the tile kernels "
+                                 "pre-filter on f16 MFMA with f32 accumulation where am_knn_path/am_prdc_path >= 2 and every "
+                                 "undecided pair is re-evaluated with the exact f32 fmaf chain.  KD (subsets of >= 512 rows, "
+                                 "D >= 128, degree 3): every gathered row is split into two f16 planes (hi = rn16(x), lo = "
+                                 "rn16(x - hi), ~22 significant bits) and the dot products are <hi,hi'> + <lo,hi'> + <hi,lo'> "
+                                 "on the f16 MFMA with f32 accumulation: error of a dot product <= ~3 * 2^-22 |x||y| (one f32 "
+                                 "rounding's worth; the reference forms them in f32 too), kernel values and all sums in f64.  "
+                                 "Statistics: exact f32 products on the f32 MFMA, f64 accumulation.  FAD: f64 throughout.",
+                   "persisting": "between steps nothing of the RESULT is cached (statistics, radii, counts, KD values and the "
+                                 "Frechet solve are recomputed); what survives is allocation and setup: torch's caching "
+                                 "allocator and the evaluate workspace (hip_ops._eval_workspace), the KD subset index table "
+                                 "on the device (a pure function of (n1, n2, S, m, seed): metrics/kd.py device_subset_indices), "
+                                 "code objects and - with several ranks - the communicators.  `first_call` (--full) times a "
+                                 "step without them."},
+        "result": result,
+    }
 
 
 def scale_model_prediction(world, n, d, k, measured_ms):
@@ -893,6 +929,8 @@ def run_e2e(args, am, dev, world, rank, fence, n_ranks_seen=1):
     else:
         fwd, synth = clock["forward"], host["t"]
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, result)
         windows = 2 * pairs                       # reference + candidate pairs, one 5 s window each
         print(json.dumps({
             "metric": "APA+FAD end-to-end pairs/sec (audio -> embedder -> device aggregation -> metrics)",

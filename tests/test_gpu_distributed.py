@@ -221,7 +221,8 @@ def test_bench_multi_rank_launch(ranks, rows, dim, plain):
     import json
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    common = ["--steps", "1", "--warmup", "1", "--rows", str(rows), "--dim", str(dim), "--no-cpu-baseline"]
+    # --full: the schedules, roofline, exchange and process_cold records checked below are not part of a plain run
+    common = ["--steps", "1", "--warmup", "1", "--rows", str(rows), "--dim", str(dim), "--full", "--no-cpu-baseline"]
     env = dict(os.environ, AM_BENCH_DEVICE="0", AM_BENCH_BACKEND="gloo")
     if plain == "c-entry":          # every rank's timed step = ONE library call (am_evaluate_sharded_f32), its collectives hooks over gloo
         common = common + ["--c-entry"]

@@ -7,7 +7,7 @@ TAG=${1:-r4}
 OUT=gpurun_out/checks_${TAG}
 mkdir -p "$OUT"
 timeout 2400 python -m pytest tests -q -m gpu 2>&1 | tail -12 > "$OUT/pytest_gpu.txt"
-timeout 900 python bench.py --steps 20 --warmup 3 > "$OUT/bench_n1.json" 2> "$OUT/bench_n1.err"
+timeout 900 python bench.py --steps 20 --warmup 3 --full > "$OUT/bench_n1.json" 2> "$OUT/bench_n1.err"
 {
 echo "# python bench.py --gpus N (plain: bench.py starts its own ranks through torch.distributed.run) at the FULL bench size"
 echo "# (2 x 100000 x 512, k = 5), every rank on cuda:0 over gloo (AM_BENCH_DEVICE=0 AM_BENCH_BACKEND=gloo: a 1-GPU box cannot host"
@@ -15,7 +15,7 @@ echo "# N RCCL ranks).  Times are meaningless (N processes share one GPU, gloo s
 echo "# reproduce the 1-rank result and the fixture."
 echo "# ranks n_ranks_seen  result  result_check.ok"
 for n in 8 4 2; do
-  AM_BENCH_DEVICE=0 AM_BENCH_BACKEND=gloo timeout 900 python bench.py --gpus $n --steps 1 --warmup 1 --no-cpu-baseline --no-variants 2> "$OUT/bench_n$n.err" | python3 -c "
+  AM_BENCH_DEVICE=0 AM_BENCH_BACKEND=gloo timeout 900 python bench.py --gpus $n --steps 1 --warmup 1 --full --no-cpu-baseline --no-variants 2> "$OUT/bench_n$n.err" | python3 -c "
 import json, sys
 for line in sys.stdin:
     if line.startswith('{'):
