@@ -442,6 +442,17 @@ static size_t kd_wide_ws(int S, int m, int D) {
 
 constexpr size_t KD_LDS_BYTES = ENGINE_LDS_FLOATS * sizeof(float);
 
+// the form run_kd takes for a shape (am_kd_path): a function of the shapes alone
+enum KdRoute { KD_TILE = 0, KD_TILE_TAIL = 1, KD_GENERIC = 2, KD_SPLIT = 3 };
+static bool kd_generic(int64_t N1, int64_t ldx, int64_t N2, int64_t ldy) {   // one buffer descriptor cannot span a matrix
+    return (uint64_t)N1 * (uint64_t)ldx * 4u >= 0xffffffffull || (uint64_t)N2 * (uint64_t)ldy * 4u >= 0xffffffffull;
+}
+static KdRoute kd_route(int64_t N1, int64_t ldx, int64_t N2, int64_t ldy, int D, int S, int m, int degree, int rbf) {
+    if (kd_wide_eligible(S, m, D, rbf, degree)) return KD_SPLIT;
+    if (kd_generic(N1, ldx, N2, ldy)) return KD_GENERIC;
+    return (D % BK) != 0 ? KD_TILE_TAIL : KD_TILE;
+}
+
 static int run_kd(const float* X, int64_t N1, int64_t ldx, const float* Y, int64_t N2, int64_t ldy, int D, const int64_t* idx1,
                   const int64_t* idx2, int S, int m, double gamma, double coef0, int degree, int rbf, double* out_mmd, void* ws,
                   size_t ws_bytes, hipStream_t st) {
@@ -451,7 +462,8 @@ static int run_kd(const float* X, int64_t N1, int64_t ldx, const float* Y, int64
     AM_REQUIRE(m <= N1 && m <= N2, AM_ERR_BAD_SHAPE, "subset size %d exceeds a set size", m);
     AM_REQUIRE(aligned16(X) && aligned16(Y) && ldx % 4 == 0 && ldy % 4 == 0 && ldx >= D && ldy >= D, AM_ERR_BAD_ARG,
                "X/Y must be 16-byte aligned with ld %% 4 == 0 and ld >= D");
-    if (kd_wide_eligible(S, m, D, rbf, degree)) {        // split-f16 form on the 256 x 256 engine
+    const KdRoute route = kd_route(N1, ldx, N2, ldy, D, S, m, degree, rbf);
+    if (route == KD_SPLIT) {                              // split-f16 form on the 256 x 256 engine
         const int MP = (int)ceil_div(m, KW) * KW, DP = (int)ceil_div(D, 64) * 64, T = MP / KW;
         const int ntri = T * (T + 1) / 2, per_subset = 2 * ntri + T * T;
         Carver c(ws, ws_bytes);
@@ -491,8 +503,7 @@ static int run_kd(const float* X, int64_t N1, int64_t ldx, const float* Y, int64
         hipLaunchKernelGGL(kd_gather_norms_kernel, dim3((unsigned)ceil_div(total, 4)), dim3(256), 0, st, Y, ldy, D, idx2, total, n2);
         AM_LAUNCH_CHECK();
     }
-    const bool generic = (uint64_t)N1 * (uint64_t)ldx * 4u >= 0xffffffffull || (uint64_t)N2 * (uint64_t)ldy * 4u >= 0xffffffffull;
-    const int mode = (((D % BK) != 0 && !generic) ? 1 : 0) | (rbf ? 2 : 0) | (generic ? 4 : 0);
+    const int mode = (route == KD_TILE_TAIL ? 1 : 0) | (rbf ? 2 : 0) | (route == KD_GENERIC ? 4 : 0);
     auto launch = [&](auto kernel) -> int {
         AM_HIP_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), (int)KD_LDS_BYTES));
         hipLaunchKernelGGL(kernel, dim3((unsigned)((int64_t)S * per_subset)), dim3(ENGINE_THREADS), KD_LDS_BYTES, st,
@@ -545,6 +556,14 @@ extern "C" int am_kd_poly_f32(const float* X, int64_t N1, int64_t ldx, const flo
     AM_REQUIRE(degree >= 0 && degree <= 16, AM_ERR_BAD_ARG, "degree %d outside [0, 16]", degree);
     return run_kd(X, N1, ldx, Y, N2, ldy, D, idx1, idx2, S, m, gamma, coef0, degree, 0, out_mmd, ws, ws_bytes,
                   static_cast<hipStream_t>(stream));
+}
+
+// which form am_kd_poly_f32 (rbf = 0) / am_kd_rbf_f32 (rbf = 1) take for a shape: 0 f32 tile form, 1 the same with an
+// inner-dimension tail, 2 generic pointer form (a matrix of >= 4 GiB), 3 split-f16 form; -1 for shapes the entry points reject
+extern "C" int am_kd_path(int64_t N1, int64_t ldx, int64_t N2, int64_t ldy, int D, int m, int degree, int rbf) {
+    if (N1 < 1 || N2 < 1 || D < 1 || m < 1 || m > N1 || m > N2 || ldx < D || ldy < D) return -1;
+    if (!rbf && (degree < 0 || degree > 16)) return -1;
+    return (int)kd_route(N1, ldx, N2, ldy, D, 1, m, rbf ? 0 : degree, rbf ? 1 : 0);
 }
 
 extern "C" size_t am_kd_rbf_workspace_bytes(int S, int m) {

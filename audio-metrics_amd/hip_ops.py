@@ -580,6 +580,15 @@ def prdc_path(n_ref, n_cand, d):
     return int(_lib.load().am_prdc_path(int(n_ref), int(n_cand), int(d)))
 
 
+KD_TILE, KD_TILE_TAIL, KD_GENERIC, KD_SPLIT = 0, 1, 2, 3
+
+
+def kd_path(n1, ldx, n2, ldy, d, m, degree=3, rbf=False):
+    """Form of the float32 kernel distance for a shape (am_kd_path): 0 f32 tile kernel, 1 the same with an inner-dimension
+    tail, 2 generic pointer form (a matrix of >= 4 GiB), 3 split-f16 form; -1 for shapes the entry points reject."""
+    return int(_lib.load().am_kd_path(int(n1), int(ldx), int(n2), int(ldy), int(d), int(m), int(degree), 1 if rbf else 0))
+
+
 def filter_engine(d):
     """Tile engine of the path-3 filter kernels for rows of d elements: 1 operand-stationary (pstat, D <= 512), 2 the same as two
     256-thread workgroups per CU (pstat64, D <= 128), 0 streamed (wide)."""

@@ -450,6 +450,11 @@ int am_kernel_clock_enable(int on);
 int am_kernel_clock_read(int kernel, int64_t* launches, double* total_ms);
 int am_knn_path(int64_t N, int64_t M, int D, int k, int self);
 int am_prdc_path(int64_t Nr, int64_t Nc, int D);
+/* am_kd_path: which form am_kd_poly_f32 (rbf = 0) / am_kd_rbf_f32 (rbf = 1) take for a shape (set sizes, row strides in
+ * elements, feature width, subset size, polynomial degree): 0 = f32 tile kernel, 1 = the same with an inner-dimension tail
+ * (D % 32 != 0), 2 = generic pointer form (N * ld * 4 bytes of either set >= 4 GiB), 3 = split-f16 form (polynomial,
+ * degree 3, m >= 512, 128 <= D <= 8192); -1 for shapes the entry points reject.  float64 rows take am_kd_*_f64 instead. */
+int am_kd_path(int64_t N1, int64_t ldx, int64_t N2, int64_t ldy, int D, int m, int degree, int rbf);
 /* form 3 has three tile engines, chosen by the row length alone: 1 = operand-stationary (csrc/pstat_engine.h: the workgroup's
  * 256-row block held in registers, kernels knn_pstat_kernel / cross_pstat_kernel; rows of up to 512 elements),
  * 2 = the same as two independent 256-thread workgroups per CU whose waves own two row tiles (pstat64_pipeline: kernels

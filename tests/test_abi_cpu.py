@@ -66,6 +66,39 @@ def test_deprecated_kd_workspace_query_is_answered_with_an_error_code():
     assert str(new) in msg and "am_kd_poly_workspace_bytes" in msg, msg
 
 
+def test_kd_path_threshold_table():
+    """am_kd_path answers from the predicates run_kd dispatches on (host arithmetic, no device): both sides of every
+    threshold - m = 512 and 128 <= D <= 8192 for the split-f16 form (polynomial degree 3 only), D % 32 for the tail
+    kernel, and N * ld * 4 bytes = 0xffffffff for the generic pointer form."""
+    import audio_metrics_amd as am
+    path = am.hip_ops.kd_path
+    n = 5000
+    # split-f16 form: m >= 512, 128 <= D <= 8192, degree 3, polynomial
+    assert path(n, 512, n, 512, 512, 511, 3) == 0 and path(n, 512, n, 512, 512, 512, 3) == 3
+    assert path(n, 128, n, 128, 128, 1000, 3) == 3 and path(n, 128, n, 128, 127, 1000, 3) == 1
+    assert path(n, 8192, n, 8192, 8192, 1000, 3) == 3 and path(n, 8196, n, 8196, 8193, 1000, 3) == 1
+    assert path(n, 8224, n, 8224, 8224, 1000, 3) == 0
+    assert path(n, 200, n, 200, 200, 600, 3) == 3 and path(n, 200, n, 200, 200, 600, 2) == 1       # any D in range
+    for degree in (0, 1, 2, 4, 16):
+        assert path(n, 512, n, 512, 512, 1000, degree) == 0
+    assert path(n, 512, n, 512, 512, 1000, 3, rbf=True) == 0 and path(n, 100, n, 100, 100, 1000, rbf=True) == 1
+    # tail kernel: D % 32 != 0 below the split form's range
+    for d, want in ((1, 1), (31, 1), (32, 0), (33, 1), (64, 0), (100, 1)):
+        assert path(n, (d + 3) // 4 * 4, n, (d + 3) // 4 * 4, d, 300, 3) == want, d
+    assert path(n, 132, n, 132, 100, 300, 3) == 1                          # a wider row stride does not change the form
+    # the 4 GiB line: one buffer descriptor spans N * ld * 4 < 0xffffffff bytes (either set)
+    below, at = (1 << 24) - 1, 1 << 24
+    assert path(below, 64, below, 64, 64, 200, 3) == 0 and path(below, 64, below, 64, 64, 200, 3, rbf=True) == 0
+    assert path(at, 64, at, 64, 64, 200, 3) == 2 and path(at, 64, 1000, 64, 64, 200, 3, rbf=True) == 2
+    assert path(1000, 64, at, 64, 64, 200, 3) == 2
+    assert path(10737418, 100, 1000, 100, 100, 200, 3) == 1 and path(10737419, 100, 1000, 100, 100, 200, 3) == 2
+    assert path(1 << 23, 128, 1 << 23, 128, 128, 600, 3) == 3                 # the split form gathers rows: no 4 GiB limit
+    assert path(1 << 23, 128, 1 << 23, 128, 128, 600, 2) == 2
+    # shapes the entry points reject
+    assert path(0, 64, 10, 64, 64, 1, 3) == -1 and path(10, 64, 10, 64, 64, 11, 3) == -1
+    assert path(10, 60, 10, 64, 64, 5, 3) == -1 and path(10, 64, 10, 64, 64, 5, 17) == -1
+
+
 def test_no_cpu_fallback():
     import audio_metrics_amd as am
     with pytest.raises(am._lib.HipLibraryError):
