@@ -24,6 +24,9 @@ SIGNATURES = {
     "am_stats_f64": (c_int, [_P, c_int64, c_int, c_int64, _P, _P, _P, c_size_t, _P]),
     "am_colsum_f64": (c_int, [_P, c_int64, c_int, c_int64, _P, _P, c_size_t, _P]),
     "am_scatter_f64": (c_int, [_P, c_int64, c_int, c_int64, _P, _P, _P, c_size_t, _P]),
+    "am_stats_gather_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
+    "am_stats_gather_f32": (c_int, [_P, c_int64, c_int64, c_int, _P, _P, c_int, _P, _P, _P, c_size_t, _P]),
+    "am_stats_gather_f64": (c_int, [_P, c_int64, c_int64, c_int, _P, _P, c_int, _P, _P, _P, c_size_t, _P]),
     "am_stats_merge_f64": (c_int, [c_int64, _P, _P, c_int64, _P, _P, c_int, _P, _P, _P]),
     "am_stats_push_max_rows": (c_int, []),
     "am_stats_push_f32": (c_int, [_P, c_int64, c_int, c_int64, c_int64, _P, _P, _P, _P, c_int64, _P]),
@@ -31,6 +34,8 @@ SIGNATURES = {
     "am_frechet_f64": (c_int, [_P, _P, _P, _P, c_int, c_int, c_double, _P, _P, c_size_t, _P]),
     "am_frechet_first_block": (c_int, []),
     "am_frechet_enqueue_f64": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_double, _P, _P, c_size_t, _P]),
+    "am_frechet_batch_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "am_frechet_batch_f64": (c_int, [_P, _P, _P, _P, c_int64, c_int, c_int, c_int, c_double, _P, _P, c_size_t, _P]),
     "am_apa_f64": (c_double, [c_double, c_double, c_double]),
     "am_kd_workspace_bytes": (c_size_t, [c_int, c_int]),
     "am_kd_poly_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),

@@ -19,7 +19,7 @@ from .data import AudioMetricsData
 from .embed import EmbedderPool, ItemCategory, embedding_pipeline
 from .embedders import DEFAULT_EMBEDDER, EMBEDDERS
 from .metrics.apa import apa, apa_compute_d_x_xp
-from .metrics.fad import frechet_distance
+from .metrics.fad import FAD_INF_MIN_N, FAD_INF_STEPS, frechet_distance, frechet_distance_inf
 from .metrics.kd import kernel_distance
 from .metrics.prdc import prdc
 from .mix_functions import resolve_mix_function
@@ -34,7 +34,8 @@ REFERENCE_SETS = {
 }
 PROJECTIONS = ("stem_projection", "mix_projection")
 PLAIN_STATE = ("metrics", "need_apa", "win_dur", "input_sr", "apa_d_x_xp")
-ROW_METRICS = frozenset(("kd", "precision", "prdc"))          # metrics that need the stored rows (audio_metrics.py:17)
+ROW_METRICS = frozenset(("kd", "precision", "prdc", "fad_inf"))   # metrics that need the stored rows (audio_metrics.py:17; "fad_inf"
+                                                                   # subsamples the candidate's)
 MAX_NEAREST_K = 10                                             # audio_metrics.py:263
 FUSED_METRICS = ("fad", "kd", "prdc")                          # what one am_evaluate_f32 call covers (result-key order)
 
@@ -86,7 +87,11 @@ class AudioMetrics:
     _need_embeddings = set(ROW_METRICS)
 
     def __init__(self, metrics=["apa", "fad"], n_pca=None, device_indices=None, embedder=None, mix_function=None,
-                 win_dur=5.0, input_sr=None, process_group=None, replica_dealing="round_robin"):
+                 win_dur=5.0, input_sr=None, process_group=None, replica_dealing="round_robin",
+                 fad_inf_steps=FAD_INF_STEPS, fad_inf_min_n=FAD_INF_MIN_N, fad_inf_seed=0):
+        if process_group is not None and "fad_inf" in metrics:
+            raise NotImplementedError('metric "fad_inf" subsamples the stored rows of one device; it is not implemented for '
+                                      "row-sharded sets (process_group=)")
         self._devices = _visible_devices(device_indices, process_group is not None, embedder)
         self.device = self._devices[0]                 # where statistics, stored rows and metric kernels live
         self._group = process_group
@@ -94,6 +99,7 @@ class AudioMetrics:
         self.need_apa = "apa" in metrics
         self.win_dur = win_dur
         self.input_sr = input_sr
+        self.fad_inf_steps, self.fad_inf_min_n, self.fad_inf_seed = fad_inf_steps, fad_inf_min_n, fad_inf_seed
         for name in PROJECTIONS:
             setattr(self, name, None if n_pca is None else IncrementalPCA(n_components=n_pca, device=self.device))
         self.embedder = self.get_embedder(embedder) if embedder is None or isinstance(embedder, str) else embedder
@@ -284,6 +290,10 @@ class AudioMetrics:
     def _run_fad(self, sets):
         return {"fad": frechet_distance(sets.stem_cand, sets.stem_ref)}
 
+    def _run_fad_inf(self, sets):
+        return frechet_distance_inf(sets.stem_cand, sets.stem_ref, steps=self.fad_inf_steps, min_n=self.fad_inf_min_n,
+                                    seed=self.fad_inf_seed)
+
     def _run_kd(self, sets):
         return kernel_distance(sets.stem_cand, sets.stem_ref)       # candidate is features_1 (audio_metrics.py:260)
 
@@ -358,5 +368,6 @@ class AudioMetrics:
                 setattr(self, key, value)
 
 
-METRIC_TABLE = (("fad", AudioMetrics._run_fad), ("kd", AudioMetrics._run_kd), ("prdc", AudioMetrics._run_prdc),
+METRIC_TABLE = (("fad", AudioMetrics._run_fad), ("fad_inf", AudioMetrics._run_fad_inf), ("kd", AudioMetrics._run_kd),
+                ("prdc", AudioMetrics._run_prdc),
                 ("apa", AudioMetrics._run_apa))

@@ -257,6 +257,47 @@ def stats_f64(e):
     return mean, cov
 
 
+def stats_gather(x, idx, offsets, defer_check=False):
+    """Statistics of B index-gathered subsets of the stored matrix x in one library call (am_stats_gather_f32 / _f64, by
+    the dtype of x): subset b is the rows x[idx[offsets[b]:offsets[b + 1]]].  idx: int64 device tensor, offsets: B + 1
+    host integers starting at 0.  Returns (means f64 [B, D], covs f64 [B, D, D]).  An index outside [0, N) raises
+    ValueError - the kernels never dereference it, they leave its position in the workspace's flag word.
+    defer_check=True returns (means, covs, check) without waiting for the device; the caller runs check() - the one host
+    read of the flag word - once it has queued the work that consumes the statistics."""
+    lib = _lib.load()
+    f64 = is_f64(x)
+    x = as_matrix64(x) if f64 else as_matrix(x)
+    _require_cuda(idx, "idx")
+    n, d = x.shape
+    offs = [int(o) for o in offsets]
+    b = len(offs) - 1
+    if b < 1 or offs[0] != 0 or any(offs[i + 1] <= offs[i] for i in range(b)):
+        raise ValueError(f"offsets must start at 0 and increase strictly (got {offs[:4]}{'...' if b > 3 else ''})")
+    idx = idx.to(torch.int64).contiguous()
+    _same_device(x, idx)
+    if idx.numel() < offs[-1]:
+        raise ValueError(f"idx holds {idx.numel()} entries, offsets name {offs[-1]}")
+    dev = x.device
+    means = torch.empty((b, d), dtype=torch.float64, device=dev)
+    covs = torch.empty((b, d, d), dtype=torch.float64, device=dev)
+    nb = lib.am_stats_gather_workspace_bytes(offs[-1], b, d)
+    ws = _workspace(nb, dev)
+    host_offs = (ctypes.c_int64 * (b + 1))(*offs)
+    _call(lib, "am_stats_gather_f64" if f64 else "am_stats_gather_f32", dev, _ptr(x), n, _ld64(x) if f64 else _ld(x), d, _ptr(idx),
+          ctypes.cast(host_offs, ctypes.c_void_p), b, _ptr(means), _ptr(covs), _ptr(ws), nb)
+
+    def check():
+        flag = int(ws[:8].view(torch.int64).item())          # the one host read: 1 + position of an out-of-range index, or 0
+        if flag != 0:
+            pos = flag - 1
+            raise ValueError(f"idx[{pos}] = {int(idx[pos].item())} is outside [0, {n}) (subset rows are named by stored-row index)")
+
+    if defer_check:
+        return means, covs, check
+    check()
+    return means, covs
+
+
 def colsum(e):
     lib = _lib.load()
     if is_f64(e):
@@ -389,6 +430,52 @@ def frechet(mu_x, cov_x, mu_y, cov_y, max_iter=64, tol=1e-13):
     _call(lib, "am_frechet_f64", mu_x.device, _ptr(mu_x), _ptr(cov_x), _ptr(mu_y), _ptr(cov_y), d, int(max_iter), float(tol),
                                   ctypes.cast(out, ctypes.c_void_p), _ptr(ws), nb)
     return dict(fd=out[0], tr_sqrt=out[1], iters=int(out[2]), resid=out[3])
+
+
+FRECHET_BATCH_WS_CAP = 1 << 30      # bytes of solver workspace per library call; larger batches go in chunks of sets
+
+
+def frechet_batch(mu_x, cov_x, mu_y, cov_y, max_iter=64, tol=1e-13, out=None):
+    """B Frechet distances advancing together (am_frechet_batch_f64): mu_x [B, D], cov_x [B, D, D] against mu_y [D],
+    cov_y [D, D] (one reference shared by all sets) or mu_y [B, D], cov_y [B, D, D].  Returns the list of the per-set dicts
+    frechet() returns, plus the device-side stop code under "stop".  `out` (optional, f64 device [B, 5]) receives the raw
+    records; it is written for every set even when a set with a non-finite product makes the call raise HipLibraryError."""
+    lib = _lib.load()
+    mu_x, cov_x, mu_y, cov_y = (_f64(t, "stats") for t in (mu_x, cov_x, mu_y, cov_y))
+    if mu_x.dim() != 2 or cov_x.dim() != 3:
+        raise ValueError(f"mu_x must be [B, D] and cov_x [B, D, D], got {tuple(mu_x.shape)} and {tuple(cov_x.shape)}")
+    b, d = mu_x.shape
+    shared = mu_y.dim() == 1
+    want_y = ((d,), (d, d)) if shared else ((b, d), (b, d, d))
+    if b < 1 or tuple(cov_x.shape) != (b, d, d) or (tuple(mu_y.shape), tuple(cov_y.shape)) != want_y:
+        raise ValueError(f"inconsistent shapes: mu {tuple(mu_x.shape)}/{tuple(mu_y.shape)}, "
+                         f"cov {tuple(cov_x.shape)}/{tuple(cov_y.shape)}")
+    dev = _same_device(mu_x, cov_x, mu_y, cov_y)
+    if out is None:
+        out = torch.empty((b, 5), dtype=torch.float64, device=dev)
+    elif out.dtype != torch.float64 or tuple(out.shape) != (b, 5) or not out.is_contiguous() or out.device != dev:
+        raise ValueError("out must be a contiguous float64 [B, 5] tensor on the statistics' device")
+    per_set = max(int(lib.am_frechet_batch_workspace_bytes(1, d)), 1)
+    chunk = max(1, min(b, FRECHET_BATCH_WS_CAP // per_set))
+    failure = None
+    for s0 in range(0, b, chunk):
+        s1 = min(b, s0 + chunk)
+        nb = lib.am_frechet_batch_workspace_bytes(s1 - s0, d)
+        ws = _workspace(nb, dev)
+        try:
+            _call(lib, "am_frechet_batch_f64", dev, _ptr(mu_x[s0:s1]), _ptr(cov_x[s0:s1]), _ptr(mu_y if shared else mu_y[s0:s1]),
+                  _ptr(cov_y if shared else cov_y[s0:s1]), 0 if shared else 1, s1 - s0, d, int(max_iter), float(tol), _ptr(out[s0:s1]),
+                  _ptr(ws), nb)
+        except _lib.HipLibraryError as e:                     # (a stop code 4 in this chunk; the other chunks still run)
+            failure = failure or e
+    rec = out.cpu().tolist()                                  # one device -> host copy of B x 5 doubles
+    bad = [i for i, r in enumerate(rec) if int(r[4]) == 4]
+    if bad:
+        raise _lib.HipLibraryError(f"am_frechet_batch_f64: set {bad[0]} of {b}: non-finite covariance product or trace in "
+                                   f"Newton-Schulz (sets with stop code 4: {bad})") from failure
+    if failure is not None:
+        raise failure
+    return [dict(fd=r[0], tr_sqrt=r[1], iters=int(r[2]), resid=r[3], stop=int(r[4])) for r in rec]
 
 
 class FrechetJob:

@@ -1,4 +1,5 @@
 """Frechet distance on the device (reference src/audio_metrics/metrics/fad.py:8-31)."""
+import numpy as np
 import torch
 
 from .. import hip_ops as ops
@@ -6,6 +7,9 @@ from ..data import AudioMetricsData, ensure_tensor
 
 NS_MAX_ITER = 64
 NS_TOL = 1e-13
+
+FAD_INF_STEPS = 15       # subset sizes of the extrapolation (Chong & Forster, CVPR 2020: 15 points ...
+FAD_INF_MIN_N = 5000     # ... from 5000 rows to the whole set, evenly spaced)
 
 last_info = {}     # iterations / residual of the most recent call (diagnostics)
 
@@ -50,3 +54,75 @@ def _frechet_distance(mu_x, sigma_x, mu_y, sigma_y, device=None) -> float:
     last_info.clear()
     last_info.update(res)
     return res["fd"]
+
+
+# ------------------------------------------------------------------ FAD-infinity
+def fad_inf_subset_indices(n, sizes, seed, device):
+    """One random subset of range(n) per entry of `sizes`, each drawn WITHOUT replacement and independently of the others:
+    the leading sizes[b] entries of a device-side permutation from a generator seeded with `seed` (reproducible per seed,
+    device and sizes; no host work in front of the kernels).  Returns (idx, offsets): the subsets concatenated in one int64
+    device tensor, and the B + 1 host offsets of am_stats_gather_f32."""
+    device = torch.device(device)
+    gen = torch.Generator(device=device)
+    gen.manual_seed(int(seed))
+    offsets = [0]
+    for m in sizes:
+        if not 1 <= int(m) <= int(n):
+            raise ValueError(f"subset size {int(m)} outside [1, {int(n)}]")
+        offsets.append(offsets[-1] + int(m))
+    idx = torch.empty(offsets[-1], dtype=torch.int64, device=device)
+    for b, m in enumerate(sizes):
+        idx[offsets[b]:offsets[b + 1]] = torch.randperm(int(n), generator=gen, device=device)[:int(m)]
+    return idx, offsets
+
+
+def fit_inverse_n(sizes, values):
+    """Ordinary least squares values_i ~ slope / sizes_i + intercept in f64 on the host: (intercept, slope, r2)."""
+    sizes = np.asarray(sizes, dtype=np.float64)
+    values = np.asarray(values, dtype=np.float64)
+    design = np.stack([1.0 / sizes, np.ones_like(sizes)], axis=1)
+    (slope, intercept), *_ = np.linalg.lstsq(design, values, rcond=None)
+    ss_res = float(np.sum((values - design @ np.array([slope, intercept])) ** 2))
+    ss_tot = float(np.sum((values - values.mean()) ** 2))
+    r2 = 1.0 - ss_res / ss_tot if ss_tot > 0.0 else float("nan")
+    return float(intercept), float(slope), r2
+
+
+def frechet_distance_inf(x: AudioMetricsData, y: AudioMetricsData, steps=FAD_INF_STEPS, min_n=FAD_INF_MIN_N, seed=0, device=None):
+    """Sample-size-extrapolated Frechet distance (Chong & Forster, "Effectively Unbiased FID and Inception Score", CVPR
+    2020): the distance of `steps` random subsets of x's stored rows (sizes evenly spaced from min_n to all of them)
+    against y's full-set statistics, fitted as slope / n + intercept; the intercept is the value at infinite sample size.
+    The subsets' statistics come from ONE gathered-statistics call on the stored matrix and their distances from ONE
+    batched solve.  Returns {"fad_inf", "fad_inf_slope", "fad_inf_r2"}; last_info carries the per-subset figures."""
+    rows = getattr(x, "embeddings", None)
+    n = int(rows.shape[0]) if rows is not None else (0 if getattr(x, "n", None) is None else int(x.n))
+    if int(steps) < 2:
+        raise ValueError(f"frechet_distance_inf needs at least 2 subset sizes to fit a line (steps={steps})")
+    if int(min_n) < 2 or int(min_n) > n:
+        raise ValueError(f"min_n={min_n} must lie in [2, {n}] (the subsampled set holds {n} rows)")
+    if rows is None:
+        raise ValueError(f"frechet_distance_inf subsamples the stored rows of its first argument, which keeps none "
+                         f"(n={n}, store_embeddings={getattr(x, 'store_embeddings', None)})")
+    steps, min_n = int(steps), int(min_n)
+    d = int(rows.shape[1])
+    sizes = np.linspace(min_n, n, steps).round().astype(int)
+    warn_if_rank_deficient(int(sizes[0]), getattr(y, "n", None), d,
+                           torch.float64 if rows.dtype == torch.float64 and getattr(y, "stats_rows_dtype", None) == torch.float64 else None)
+    if device is None:
+        device = rows.device if rows.is_cuda else None
+    if device is None:
+        from ..data import default_device
+        device = default_device()
+    device = torch.device(device)
+    rows = ops.as_rows(rows.to(device))
+    mu_y, cov_y = (ensure_tensor(t).to(device, torch.float64) for t in (y.mean, y.cov))
+    idx, offsets = fad_inf_subset_indices(n, sizes, seed, device)
+    means, covs, check = ops.stats_gather(rows, idx, offsets, defer_check=True)
+    res = ops.frechet_batch(means, covs, mu_y.reshape(-1), cov_y, NS_MAX_ITER, NS_TOL)
+    check()
+    fads = [r["fd"] for r in res]
+    intercept, slope, r2 = fit_inverse_n(sizes, fads)
+    last_info.clear()
+    last_info.update(sizes=[int(m) for m in sizes], fads=fads, iters=[r["iters"] for r in res], stops=[r["stop"] for r in res],
+                     resids=[r["resid"] for r in res], seed=int(seed))
+    return {"fad_inf": intercept, "fad_inf_slope": slope, "fad_inf_r2": r2}

@@ -81,6 +81,28 @@ int am_colsum_f64(const double* X, int64_t N, int D, int64_t ld,
                   double* colsum, void* ws, size_t ws_bytes, am_stream_t stream);
 int am_scatter_f64(const double* X, int64_t N, int D, int64_t ld, const double* mean,
                    double* scatter, void* ws, size_t ws_bytes, am_stream_t stream);
+/* Statistics of B index-gathered subsets of ONE stored matrix in one call (FAD-infinity: the subsets of a candidate set).
+ * Subset b is the rows X[idx[offsets[b] + j]], j < n_b = offsets[b + 1] - offsets[b]; no gathered copy is made, the rows are
+ * read whole through the index list, and the number of launches does not depend on B (the concatenated list is cut into
+ * chunks that never straddle a subset).  Numerics contract of am_stats_f32 / am_stats_f64: f64 means; float32 rows centred
+ * in f32, products on the f32 matrix cores in chains of 256 rows, f64 across; float64 rows entirely in f64.  n_b == 1 ->
+ * zero covariance; n_b == 0 -> AM_ERR_BAD_SHAPE.  Indices may repeat and come in any order.
+ *   idx      DEVICE, offsets[B] int64 entries        offsets  HOST, B + 1 entries, offsets[0] == 0, increasing
+ *   means    DEVICE [B][D]                            covs     DEVICE [B][D][D]
+ * An index outside [0, N) is never dereferenced: the row is left out and the FIRST 8 BYTES OF `ws` (an unsigned 64-bit
+ * word, zeroed by every call) receive 1 + the largest position in idx that held such an index; 0 = every index was valid.
+ * The call itself is asynchronous and returns AM_OK; the caller reads the word with the results.  X as for the plain
+ * entry points (float32: 16-byte aligned, ld % 4 == 0, and N * ld * 4 bytes below 4 GiB - the rows are addressed by 32-bit
+ * element offsets -, else AM_ERR_BAD_SHAPE; float64: any ld >= D, D <= 8192).  One workspace query serves both. */
+size_t am_stats_gather_workspace_bytes(int64_t n_total, int B, int D);
+int am_stats_gather_f32(const float* X, int64_t N, int64_t ld, int D,
+                        const int64_t* idx, const int64_t* offsets, int B,
+                        double* means, double* covs,
+                        void* ws, size_t ws_bytes, am_stream_t stream);
+int am_stats_gather_f64(const double* X, int64_t N, int64_t ld, int D,
+                        const int64_t* idx, const int64_t* offsets, int B,
+                        double* means, double* covs,
+                        void* ws, size_t ws_bytes, am_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * A3  Chan / pairwise merge of two (n, mean, cov) triples in f64
@@ -138,6 +160,22 @@ int am_frechet_enqueue_f64(const double* mu_x, const double* cov_x,
                            const double* mu_y, const double* cov_y, int D,
                            int first_iter, int n_iter, int max_iter, double tol, double* out_dev,
                            void* ws, size_t ws_bytes, am_stream_t stream);
+/* B independent Frechet distances advancing together: every launch of the Newton-Schulz chain covers all B products (the set
+ * index is a grid dimension), each set has its own state, stopping rule and stop code, and the workgroups of a set that has
+ * stopped return at once.  Blocks of am_frechet_first_block() iterations are enqueued and `stream` is SYNCHRONISED once per
+ * block for the whole batch, while some set's stop code is 0.  Per set the arithmetic is that of am_frechet_enqueue_f64
+ * (same tile order, same fixed summation orders): out_dev[b] holds the same five doubles, bit for bit.
+ *   mu_x [B][D], cov_x [B][D][D]   DEVICE
+ *   mu_y, cov_y                    DEVICE; y_stride_sets == 0: one (mu_y[D], cov_y[D][D]) shared by all sets,
+ *                                  y_stride_sets == 1: one per set, laid out as x
+ *   out_dev                        DEVICE [B][5]: { fd, tr_sqrt, iterations, residual, stop code } per set
+ * Returns AM_ERR_NO_CONVERGENCE naming the first set whose stop code is 4 (non-finite product); all B records are written
+ * in that case too.  Workspace: about 6 * B * D * D * 8 bytes. */
+size_t am_frechet_batch_workspace_bytes(int B, int D);
+int am_frechet_batch_f64(const double* mu_x, const double* cov_x,
+                         const double* mu_y, const double* cov_y, int64_t y_stride_sets,
+                         int B, int D, int max_iter, double tol, double* out_dev,
+                         void* ws, size_t ws_bytes, am_stream_t stream);
 
 /* A11 APA scalar combination (host arithmetic)  reference: apa.py:22-32 */
 double am_apa_f64(double d_y_x, double d_y_xp, double d_x_xp);
