@@ -10,6 +10,7 @@ from .data import AudioMetricsData, ensure_tensor, ensure_ndarray            # n
 from . import metrics                                                         # noqa: F401
 from .metrics.fad import frechet_distance, frechet_distance_inf               # noqa: F401
 from .metrics.kd import kernel_distance, kid_features_to_metric               # noqa: F401
+from .metrics.kad import kernel_audio_distance                                # noqa: F401
 from .metrics.prdc import prdc, nearest_neighbour_distances                   # noqa: F401
 from .metrics.apa import apa, apa_compute_d_x_xp                              # noqa: F401
 

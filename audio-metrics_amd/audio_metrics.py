@@ -20,6 +20,7 @@ from .embed import EmbedderPool, ItemCategory, embedding_pipeline
 from .embedders import DEFAULT_EMBEDDER, EMBEDDERS
 from .metrics.apa import apa, apa_compute_d_x_xp
 from .metrics.fad import FAD_INF_MIN_N, FAD_INF_STEPS, frechet_distance, frechet_distance_inf
+from .metrics.kad import KAD_SCALE, kernel_audio_distance
 from .metrics.kd import kernel_distance
 from .metrics.prdc import prdc
 from .mix_functions import resolve_mix_function
@@ -34,8 +35,8 @@ REFERENCE_SETS = {
 }
 PROJECTIONS = ("stem_projection", "mix_projection")
 PLAIN_STATE = ("metrics", "need_apa", "win_dur", "input_sr", "apa_d_x_xp")
-ROW_METRICS = frozenset(("kd", "precision", "prdc", "fad_inf"))   # metrics that need the stored rows (audio_metrics.py:17; "fad_inf"
-                                                                   # subsamples the candidate's)
+ROW_METRICS = frozenset(("kd", "precision", "prdc", "fad_inf", "kad"))   # metrics that need the stored rows (audio_metrics.py:17;
+                                                                          # "fad_inf" subsamples the candidate's, "kad" sweeps both sets)
 MAX_NEAREST_K = 10                                             # audio_metrics.py:263
 FUSED_METRICS = ("fad", "kd", "prdc")                          # what one am_evaluate_f32 call covers (result-key order)
 
@@ -88,10 +89,16 @@ class AudioMetrics:
 
     def __init__(self, metrics=["apa", "fad"], n_pca=None, device_indices=None, embedder=None, mix_function=None,
                  win_dur=5.0, input_sr=None, process_group=None, replica_dealing="round_robin",
-                 fad_inf_steps=FAD_INF_STEPS, fad_inf_min_n=FAD_INF_MIN_N, fad_inf_seed=0):
+                 fad_inf_steps=FAD_INF_STEPS, fad_inf_min_n=FAD_INF_MIN_N, fad_inf_seed=0, kad_bandwidth=None, kad_scale=KAD_SCALE):
         if process_group is not None and "fad_inf" in metrics:
             raise NotImplementedError('metric "fad_inf" subsamples the stored rows of one device; it is not implemented for '
                                       "row-sharded sets (process_group=)")
+        if process_group is not None and "kad" in metrics:
+            raise NotImplementedError('metric "kad" sweeps the stored rows of one device (whole-set kernel sums and a median over '
+                                      "all reference pairs); it is not implemented for row-sharded sets (process_group=)")
+        if n_pca is not None and "kad" in metrics:
+            raise NotImplementedError('metric "kad" takes float32 rows; the PCA projection (n_pca=) hands on float64 rows, whose '
+                                      "matrix-core form of the select and the kernel sums is not implemented")
         self._devices = _visible_devices(device_indices, process_group is not None, embedder)
         self.device = self._devices[0]                 # where statistics, stored rows and metric kernels live
         self._group = process_group
@@ -100,6 +107,7 @@ class AudioMetrics:
         self.win_dur = win_dur
         self.input_sr = input_sr
         self.fad_inf_steps, self.fad_inf_min_n, self.fad_inf_seed = fad_inf_steps, fad_inf_min_n, fad_inf_seed
+        self.kad_bandwidth, self.kad_scale = kad_bandwidth, kad_scale
         for name in PROJECTIONS:
             setattr(self, name, None if n_pca is None else IncrementalPCA(n_components=n_pca, device=self.device))
         self.embedder = self.get_embedder(embedder) if embedder is None or isinstance(embedder, str) else embedder
@@ -238,7 +246,7 @@ class AudioMetrics:
             return self._evaluate_sharded(sets)
         fused = self._run_fused(sets)                  # None: the one-call form does not apply - every metric runs on its own
         result = dict(fused) if fused is not None else {}
-        for key, run in METRIC_TABLE:
+        for key, run in EVALUATION_TABLE:
             if key in self.metrics and not (fused is not None and key in FUSED_METRICS):
                 result.update(run(self, sets))
         return result
@@ -296,6 +304,9 @@ class AudioMetrics:
 
     def _run_kd(self, sets):
         return kernel_distance(sets.stem_cand, sets.stem_ref)       # candidate is features_1 (audio_metrics.py:260)
+
+    def _run_kad(self, sets):
+        return kernel_audio_distance(sets.stem_cand, sets.stem_ref, bandwidth=self.kad_bandwidth, scale=self.kad_scale)
 
     def _run_prdc(self, sets):
         k = max(1, min(MAX_NEAREST_K, len(sets.stem_ref), len(sets.stem_cand)))
@@ -371,3 +382,7 @@ class AudioMetrics:
 METRIC_TABLE = (("fad", AudioMetrics._run_fad), ("fad_inf", AudioMetrics._run_fad_inf), ("kd", AudioMetrics._run_kd),
                 ("prdc", AudioMetrics._run_prdc),
                 ("apa", AudioMetrics._run_apa))
+# what evaluate() walks: the reference's metrics in its result-key order (METRIC_TABLE) with this build's whole-set kernel
+# distance after the subset one
+EVALUATION_TABLE = tuple(row for entry in METRIC_TABLE
+                         for row in ((entry, ("kad", AudioMetrics._run_kad)) if entry[0] == "kd" else (entry,)))

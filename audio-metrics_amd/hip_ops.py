@@ -587,6 +587,58 @@ def kd_rbf(x, y, idx1, idx2, sigma):
     return out
 
 
+# ------------------------------------------------------------------ kernel audio distance
+MMD_XX, MMD_YY, MMD_XY = 1, 2, 4                       # enum am_mmd_block
+
+
+def pairwise_select_sq(x, rank=None):
+    """The element of 0-based `rank` (None: the lower median, torch.median's convention) among the float32 squared
+    distances of the N (N - 1) / 2 unordered row pairs of x, as a 0-dim float32 DEVICE tensor: an exact radix select over
+    recomputed Gram tiles (am_pairwise_select_f32), stream-ordered, no host synchronisation."""
+    lib = _lib.load()
+    if is_f64(x):
+        raise NotImplementedError("pairwise_select_sq takes float32 rows (the float64 matrix-core form is not implemented)")
+    x = as_matrix(x, "x")
+    n, d = x.shape
+    out = torch.empty((), dtype=torch.float32, device=x.device)
+    nb = lib.am_pairwise_select_workspace_bytes(n, d)
+    ws = _workspace(nb, x.device)
+    _call(lib, "am_pairwise_select_f32", x.device, _ptr(x), n, _ld(x), d, -1 if rank is None else int(rank), _ptr(out),
+          _ptr(ws), nb)
+    return out
+
+
+def mmd_rbf_sums(x, y, bw2=None, gamma=None, blocks=7, out=None):
+    """float64[3] device tensor {Sxx, Syy, Sxy} of K = exp(-|a - b|^2 gamma) over the whole sets (am_mmd_rbf_f32): Sxx / Syy
+    over ordered pairs i != j, Sxy over all pairs.  `bw2`: a float32 DEVICE scalar (gamma = 0.5 / bw2 is formed on the
+    device - the output of pairwise_select_sq, no host round trip) or `gamma`: a number.  Only the slots named by `blocks`
+    (MMD_XX | MMD_YY | MMD_XY) are written; the others keep what `out` held (NaN in a fresh tensor)."""
+    lib = _lib.load()
+    if is_f64(x) or is_f64(y):
+        raise NotImplementedError("mmd_rbf_sums takes float32 rows (the float64 matrix-core form is not implemented)")
+    if (bw2 is None) == (gamma is None):
+        raise ValueError("exactly one of bw2 (device scalar) and gamma (number) must be given")
+    x, y = as_matrix(x, "x"), as_matrix(y, "y")
+    dev = _same_device(x, y)
+    if x.shape[1] != y.shape[1]:
+        raise ValueError(f"feature widths differ: {x.shape[1]} and {y.shape[1]}")
+    if out is None:
+        out = torch.full((3,), float("nan"), dtype=torch.float64, device=dev)
+    elif not (out.is_cuda and out.dtype == torch.float64 and out.numel() == 3 and out.is_contiguous()):
+        raise ValueError("out must be a contiguous float64[3] device tensor")
+    if bw2 is not None:
+        _require_cuda(bw2, "bw2")
+        if bw2.dtype != torch.float32 or bw2.numel() != 1:
+            raise ValueError("bw2 must be a float32 device scalar")
+    blocks = int(blocks)
+    nb = lib.am_mmd_rbf_workspace_bytes(x.shape[0], y.shape[0], x.shape[1], blocks)
+    ws = _workspace(nb, dev)
+    _call(lib, "am_mmd_rbf_f32", dev, _ptr(x), x.shape[0], _ld(x), _ptr(y), y.shape[0], _ld(y), x.shape[1],
+          _ptr(bw2) if bw2 is not None else ctypes.c_void_p(None), 0.0 if gamma is None else float(gamma), blocks, _ptr(out),
+          _ptr(ws), nb)
+    return out
+
+
 # ------------------------------------------------------------------ PRDC
 class PreparedSet:
     """What every PRDC entry point derives from a set before its tile kernels run - squared row norms, their maximum, the

@@ -1,0 +1,114 @@
+"""Kernel Audio Distance (Chung et al. 2025, "KAD: No More FAD!"): the unbiased MMD^2 between the WHOLE candidate set and
+the WHOLE reference set under a Gaussian kernel whose bandwidth is the median pairwise distance of the reference set.
+
+  d2(a, b) = max((|a|^2 + |b|^2) - 2 a.b, 0)            f64, f64 norms, f32 matrix-core dot product
+  bw^2     = rn32(lower median of d2 over the m (m - 1) / 2 unordered reference pairs)        (ops.pairwise_select_sq)
+  k(a, b)  = exp(-d2(a, b) / (2 bw^2))                                                        (ops.mmd_rbf_sums)
+  mmd^2    = Sxx / (n (n - 1)) + Syy / (m (m - 1)) - 2 Sxy / (n m),     kad = scale * mmd^2
+
+Unlike the subset kernel distance (metrics/kd.py) nothing is sampled, so the value has no seed and no subset size, and -
+the reason the field adopted it - no bias in the sample size.  The reference-side half (the median and Syy) depends on
+the reference set alone and is kept on it: a big cached reference against a small candidate set costs the cross block."""
+import math
+import struct
+
+import torch
+
+from .. import hip_ops as ops
+from ..data import AudioMetricsData
+
+KAD_SCALE = 100.0
+CACHE_ATTR = "_kad_cache"         # on the reference AudioMetricsData; NOT part of serialize(): the file layout stays as it is
+
+
+def _gamma_bits(gamma):
+    return struct.pack("<d", float(gamma))
+
+
+class _ReferenceCache:
+    """What KAD derives from a reference set alone, valid for exactly the rows it was computed from: (number of rows,
+    _content_version) - every append bumps the version, so both entries are recomputed after an add (the radii cache's
+    "survives appends" quirk is the reference's own and is not copied here)."""
+
+    def __init__(self, key):
+        self.key = key
+        self.bw2 = None            # 0-dim float32 device tensor: median squared distance
+        self.bw2_host = None       # its value, once a result has been read back
+        self.syy = {}              # gamma bits -> 0-dim float64 device tensor
+
+
+def reference_cache(y):
+    rows = y.embeddings
+    key = (int(rows.shape[0]), int(getattr(y, "_content_version", -1)))
+    cache = getattr(y, CACHE_ATTR, None)
+    if cache is None or cache.key != key:
+        cache = _ReferenceCache(key)
+        setattr(y, CACHE_ATTR, cache)
+    return cache
+
+
+def _rows_of(data, name):
+    rows = getattr(data, "embeddings", None)
+    if rows is None:
+        raise ValueError(f"kernel_audio_distance needs the stored rows of its {name} set, which keeps none "
+                         f"(store_embeddings={getattr(data, 'store_embeddings', None)})")
+    if rows.shape[0] < 2:
+        raise ValueError(f"kernel_audio_distance needs at least 2 rows in the {name} set (it holds {rows.shape[0]}): the "
+                         "unbiased MMD^2 divides by n (n - 1)")
+    if rows.dtype == torch.float64:
+        raise NotImplementedError(f"kernel_audio_distance: the {name} set holds float64 rows; the float64 matrix-core form "
+                                  "of the select and of the kernel sums is not implemented")
+    return rows
+
+
+def kernel_audio_distance(x: AudioMetricsData, y: AudioMetricsData, bandwidth=None, scale=KAD_SCALE):
+    """KAD of candidate set `x` against reference set `y`.  bandwidth=None: the median pairwise distance of `y`; a number
+    fixes it.  Returns {"kad": scale * mmd^2, "kad_mmd2": mmd^2, "kad_bandwidth": bw}."""
+    ex, ey = _rows_of(x, "candidate"), _rows_of(y, "reference")
+    if ex.shape[1] != ey.shape[1]:
+        raise ValueError(f"feature widths differ: {ex.shape[1]} and {ey.shape[1]}")
+    gamma = None
+    if bandwidth is not None:
+        bw = float(bandwidth)
+        if not math.isfinite(bw) or bw <= 0.0:
+            raise ValueError(f"bandwidth={bandwidth!r} must be a finite positive number")
+        gamma = 1.0 / (2.0 * bw * bw)
+    n, m = int(ex.shape[0]), int(ey.shape[0])
+    cache = reference_cache(y)
+    bw2_dev = None
+    if gamma is None:
+        if cache.bw2 is None:
+            cache.bw2 = ops.pairwise_select_sq(ey)
+        bw2_dev = cache.bw2
+        if cache.bw2_host is not None:                     # the bits the device forms from the same float32: 0.5 / (double)bw2
+            _check_bandwidth(cache.bw2_host)
+            gamma = 0.5 / cache.bw2_host
+    syy = cache.syy.get(_gamma_bits(gamma)) if gamma is not None else None
+    blocks = ops.MMD_XX | ops.MMD_XY | (0 if syy is not None else ops.MMD_YY)
+    if bw2_dev is not None:
+        sums = ops.mmd_rbf_sums(ex, ey, bw2=bw2_dev, blocks=blocks)
+    else:
+        sums = ops.mmd_rbf_sums(ex, ey, gamma=gamma, blocks=blocks)
+    fresh_syy = syy is None
+    if fresh_syy:
+        syy = sums[1].clone()
+    tail = bw2_dev.to(torch.float64) if bw2_dev is not None else torch.zeros((), dtype=torch.float64, device=sums.device)
+    sxx, sxy, syy_v, bw2_v = torch.stack([sums[0], sums[2], syy, tail]).cpu().tolist()       # the one read-back
+    if bw2_dev is not None:
+        cache.bw2_host = bw2_v
+        _check_bandwidth(bw2_v)
+        gamma = 0.5 / bw2_v
+        bw = math.sqrt(bw2_v)
+    if fresh_syy:
+        cache.syy[_gamma_bits(gamma)] = syy
+    mmd2 = sxx / (n * (n - 1.0)) + syy_v / (m * (m - 1.0)) - 2.0 * sxy / (float(n) * m)
+    return {"kad": float(scale) * mmd2, "kad_mmd2": mmd2, "kad_bandwidth": bw}
+
+
+def _check_bandwidth(bw2):
+    if not math.isfinite(bw2):
+        raise ValueError("kernel_audio_distance: the median pairwise distance of the reference set is not finite - at least "
+                         "half of its row pairs involve a row with non-finite elements (NaN / inf embeddings)")
+    if bw2 <= 0.0:
+        raise ValueError("kernel_audio_distance: the median pairwise distance of the reference set is 0 - more than half of "
+                         "its row pairs coincide (duplicate rows); pass bandwidth= to fix the kernel width")

@@ -224,6 +224,40 @@ int am_kd_rbf_f32(const float* X, int64_t N1, int64_t ldx,
                   double* out_mmd, void* ws, size_t ws_bytes, am_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Kernel Audio Distance (Chung et al. 2025): unbiased MMD^2 between two WHOLE sets with a Gaussian kernel whose
+ * bandwidth is the median pairwise distance of the reference set.  Two building blocks (csrc/kad.hip, f32 tile engine):
+ *
+ * Squared distance of a pair, in both:  d2 = max((|a|^2 + |b|^2) - 2 dot(a, b), 0)  in f64, with f64 squared norms and
+ * the f32 matrix-core dot product (the arithmetic of the RBF kernel distance above).
+ *
+ * am_pairwise_select_f32: *out_d2 (DEVICE) = the element of 0-based `rank` among the float32 keys rn32(d2(x_i, x_j)) of the
+ *   N (N - 1) / 2 unordered pairs i < j in ascending order; rank < 0 = the lower median, rank (P - 1) / 2
+ *   (torch.median's convention).  Rounding is monotone: the result equals the rounded f64 order statistic.  A pair whose
+ *   d2 is NaN or +inf (a non-finite row) has key +inf.  Exact: a radix select in three histogram passes (11 / 10 / 10
+ *   bits) over the recomputed upper-triangular tiles, bin totals in 64 bits; no N x N matrix exists at any time.  The
+ *   whole call is stream-ordered, never synchronises with the host and returns no value to it.
+ *   N < 2 or rank >= P -> AM_ERR_BAD_SHAPE; N * ld * 4 bytes >= 4 GiB -> AM_ERR_BAD_SHAPE (one buffer descriptor spans the
+ *   matrix, as for the gathered statistics above).
+ *
+ * am_mmd_rbf_f32: out_sums (DEVICE, 3 doubles) = {Sxx, Syy, Sxy} of K = exp(-d2 gamma):  Sxx / Syy over the ordered pairs
+ *   i != j of X / Y, Sxy over all N1 N2 pairs.  `blocks` is a mask of AM_MMD_XX | AM_MMD_YY | AM_MMD_XY; only the slots
+ *   it names are written.  bw2_dev != NULL: the kernels read gamma = 0.5 / (double)*bw2_dev on the device and ignore the
+ *   `gamma` argument - the output of the select feeds the sums with no host round trip.  Rows are read directly (no
+ *   index lists), N1 != N2 allowed, any D >= 1.  Kernel values and every sum in f64; one partial per workgroup, summed in
+ *   a fixed order: two calls on the same input give the same bits.  Size limit as for the select.
+ *   unbiased MMD^2 = Sxx / (N1 (N1 - 1)) + Syy / (N2 (N2 - 1)) - 2 Sxy / (N1 N2)   (left to the caller).
+ * ------------------------------------------------------------------------- */
+enum am_mmd_block { AM_MMD_XX = 1, AM_MMD_YY = 2, AM_MMD_XY = 4 };
+size_t am_pairwise_select_workspace_bytes(int64_t N, int D);
+int am_pairwise_select_f32(const float* X, int64_t N, int64_t ld, int D, int64_t rank,
+                           float* out_d2, void* ws, size_t ws_bytes, am_stream_t stream);
+size_t am_mmd_rbf_workspace_bytes(int64_t N1, int64_t N2, int D, unsigned blocks);
+int am_mmd_rbf_f32(const float* X, int64_t N1, int64_t ldx,
+                   const float* Y, int64_t N2, int64_t ldy, int D,
+                   const float* bw2_dev, double gamma, unsigned blocks,
+                   double* out_sums, void* ws, size_t ws_bytes, am_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * A9  k-NN radii                                reference: prdc.py:4-14, data.py:60-66
  *   out_r[i] = (k+1)-th smallest Euclidean distance from row i of X to the M
  *   rows of Y (Y == X for the reference's self-distance use; a multi-GPU

@@ -1,0 +1,234 @@
+"""Kernel Audio Distance, the part that needs no GPU: the host oracles the GPU tests lean on, the error paths of the two
+new entry points (validated before the first HIP call), their workspace queries, the "kad" row of AudioMetrics, and the
+compile-time resource check of csrc/kad.hip (no scratch memory, two workgroups per CU)."""
+import ctypes
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+import kad_reference as ka
+import kd_reference as kr
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "audio-metrics_amd", "csrc")
+BAD_ARG, BAD_SHAPE, WORKSPACE = -1, -2, -4
+FAKE = ctypes.c_void_p(0x10000)                       # 16-byte aligned, never dereferenced: the calls stop at validation
+
+
+@pytest.fixture(scope="module")
+def am():
+    import audio_metrics_amd
+    return audio_metrics_amd
+
+
+@pytest.fixture(scope="module")
+def lib(am):
+    return am._lib.load()
+
+
+# ---------------------------------------------------------------------------------------------------- oracles
+def test_weighted_order_statistic_against_brute_force():
+    rng = np.random.default_rng(5)
+    points = kr.exact_rows(rng, 7, 32)
+    counts = rng.multinomial(60 - 7, np.full(7, 1.0 / 7)) + 1
+    x = np.repeat(points, counts, axis=0)[rng.permutation(60)]
+    brute = ka.pair_values(x)
+    values, weights = ka.group_pairs(points, counts)
+    assert sum(weights) == len(brute) == 60 * 59 // 2
+    for rank in range(len(brute)):
+        assert ka.weighted_order_statistic(values, weights, rank) == brute[rank], rank
+    with pytest.raises(ValueError):
+        ka.weighted_order_statistic(values, weights, len(brute))
+
+
+def test_pair_values_and_median_convention():
+    x = kr.exact_rows(np.random.default_rng(6), 9, 16)
+    v = ka.pair_values(x)
+    direct = sorted(float(((x[i].astype(np.float64) - x[j].astype(np.float64)) ** 2).sum()) for i in range(9) for j in range(i + 1, 9))
+    assert list(v) == direct                                          # exact data: norms - 2 dot = sum of squared differences
+    med = torch.median(torch.as_tensor(v)).item()                     # torch.median: the LOWER median
+    assert med == v[ka.lower_median_rank(len(v))] and len(v) % 2 == 0
+    x[3, 0] = np.nan
+    v = ka.pair_values(x)
+    assert np.isinf(v[-8:]).all() and np.isfinite(v[:-8]).all()
+    assert ka.as_key(1e300) == np.inf
+
+
+def test_mmd_parts_against_a_direct_double_loop():
+    rng = np.random.default_rng(8)
+    x, y = kr.rbf_rows(rng, 5, 16, 10.0), kr.rbf_rows(rng, 7, 16, 10.0)
+    g = 1.0 / 200.0
+
+    def k(a, b):
+        return np.exp(-((a.astype(np.float64) - b.astype(np.float64)) ** 2).sum() * g)
+    sxx = sum(k(x[i], x[j]) for i in range(5) for j in range(5) if i != j)
+    syy = sum(k(y[i], y[j]) for i in range(7) for j in range(7) if i != j)
+    sxy = sum(k(a, b) for a in x for b in y)
+    means, scale = ka.mmd_parts(x, y, g)
+    np.testing.assert_allclose(means, [sxx / 20, syy / 42, sxy / 35], rtol=1e-14)
+    assert 0.0 < scale <= 1.0
+    np.testing.assert_allclose(ka.device_means([sxx, syy, sxy], 5, 7), means, rtol=1e-14)
+
+
+# ---------------------------------------------------------------------------------------------------- C ABI without a device
+def test_header_exports_and_signature_table_agree(am, lib):
+    with open(os.path.join(ROOT, "include", "audio_metrics_hip.h")) as f:
+        header = f.read()
+    for name in ("am_pairwise_select_workspace_bytes", "am_pairwise_select_f32", "am_mmd_rbf_workspace_bytes", "am_mmd_rbf_f32"):
+        assert re.search(r"\b%s\s*\(" % name, header), name
+        assert name in am._lib.SIGNATURES and hasattr(lib, name), name
+    assert (am.hip_ops.MMD_XX, am.hip_ops.MMD_YY, am.hip_ops.MMD_XY) == (1, 2, 4)
+    assert re.search(r"AM_MMD_XX = 1, AM_MMD_YY = 2, AM_MMD_XY = 4", header)
+
+
+def test_select_error_paths(lib):
+    n, d = 1000, 64
+    nb = lib.am_pairwise_select_workspace_bytes(n, d)
+    pairs = n * (n - 1) // 2
+
+    def call(x=FAKE, n=n, ld=d, d=d, rank=-1, out=FAKE, ws=FAKE, nb=nb):
+        return lib.am_pairwise_select_f32(x, n, ld, d, rank, out, ws, nb, None)
+    assert call(x=None) == BAD_ARG and call(out=None) == BAD_ARG
+    assert "null" in lib.am_last_error().decode()
+    assert call(n=1) == BAD_SHAPE and call(n=0) == BAD_SHAPE and call(d=0) == BAD_SHAPE
+    assert call(rank=pairs) == BAD_SHAPE and str(pairs) in lib.am_last_error().decode()
+    assert call(ld=d - 4) == BAD_ARG and call(ld=d + 1) == BAD_ARG and call(x=ctypes.c_void_p(0x10004)) == BAD_ARG
+    # one buffer descriptor spans the matrix: N * ld * 4 bytes must stay below 4 GiB
+    big = 1 << 24
+    assert call(n=big, nb=lib.am_pairwise_select_workspace_bytes(big, d)) == BAD_SHAPE and "4 GiB" in lib.am_last_error().decode()
+    assert call(nb=nb - 1) == WORKSPACE and str(nb) in lib.am_last_error().decode()
+    assert call(ws=None) == WORKSPACE and call(nb=0) == WORKSPACE
+
+
+def test_mmd_error_paths(lib):
+    n1, n2, d = 1000, 300, 64
+    nb = lib.am_mmd_rbf_workspace_bytes(n1, n2, d, 7)
+
+    def call(x=FAKE, n1=n1, ldx=d, y=FAKE, n2=n2, ldy=d, d=d, bw2=None, gamma=0.5, blocks=7, out=FAKE, ws=FAKE, nb=nb):
+        return lib.am_mmd_rbf_f32(x, n1, ldx, y, n2, ldy, d, bw2, gamma, blocks, out, ws, nb, None)
+    assert call(x=None) == BAD_ARG and call(y=None) == BAD_ARG and call(out=None) == BAD_ARG
+    assert call(blocks=0) == BAD_ARG and call(blocks=8) == BAD_ARG
+    assert call(n1=0) == BAD_SHAPE and call(n2=0) == BAD_SHAPE and call(d=0) == BAD_SHAPE
+    assert call(ldx=d - 4) == BAD_ARG and call(ldy=d + 2) == BAD_ARG
+    assert call(gamma=-1.0) == BAD_ARG
+    big = 1 << 24
+    assert call(n1=big, nb=1 << 40) == BAD_SHAPE and "4 GiB" in lib.am_last_error().decode()
+    assert call(n2=big, nb=1 << 40) == BAD_SHAPE
+    assert call(nb=nb - 1) == WORKSPACE and str(nb) in lib.am_last_error().decode()
+    assert call(ws=None) == WORKSPACE
+    # a mask needs the workspace of its own blocks only
+    assert call(blocks=4, nb=lib.am_mmd_rbf_workspace_bytes(n1, n2, d, 4) - 1) == WORKSPACE
+
+
+def test_workspace_queries_are_monotone(lib):
+    for d in (32, 100, 512):
+        prev_s, prev_m = 0, 0
+        for n in (2, 129, 1000, 20_000, 100_000, 1_000_000):
+            s = lib.am_pairwise_select_workspace_bytes(n, d)
+            m = lib.am_mmd_rbf_workspace_bytes(n, n, d, 7)
+            assert s > prev_s and m > prev_m, (n, d)
+            assert s >= n * 8 and m >= 2 * n * 8                       # the f64 norms
+            prev_s, prev_m = s, m
+    assert lib.am_pairwise_select_workspace_bytes(1, 64) == 0 and lib.am_pairwise_select_workspace_bytes(10, 0) == 0
+    assert lib.am_mmd_rbf_workspace_bytes(0, 10, 64, 7) == 0 and lib.am_mmd_rbf_workspace_bytes(10, 10, 64, 0) == 0
+    full = lib.am_mmd_rbf_workspace_bytes(5000, 700, 64, 7)
+    assert all(0 < lib.am_mmd_rbf_workspace_bytes(5000, 700, 64, b) <= full for b in range(1, 7))
+
+
+# ---------------------------------------------------------------------------------------------------- front end
+class _Embedder:
+    sr = 16000
+
+    def get_device(self):
+        return torch.device("cpu")
+
+
+def _fake_one_gpu(monkeypatch):
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: True)
+    monkeypatch.setattr(torch.cuda, "device_count", lambda: 1)
+    monkeypatch.setattr(torch.cuda, "current_device", lambda: 0)
+
+
+def test_audio_metrics_row(am, monkeypatch):
+    from audio_metrics_amd import audio_metrics as front
+    assert "kad" in front.ROW_METRICS
+    keys = [k for k, _ in front.EVALUATION_TABLE]
+    assert keys.index("kad") == keys.index("kd") + 1
+    assert [k for k in keys if k != "kad"] == [k for k, _ in front.METRIC_TABLE]
+    assert "kad" not in front.FUSED_METRICS                            # the one-call form is untouched
+    assert am.kernel_audio_distance is front.kernel_audio_distance
+    _fake_one_gpu(monkeypatch)
+    kw = dict(embedder=_Embedder(), mix_function=lambda *a: None, device_indices=[0])
+    m = am.AudioMetrics(metrics=["kad"], **kw)
+    assert m.store_stem_embeddings and m.stems_mode and not m.need_apa and m.stem_reference.store_embeddings
+    assert (m.kad_bandwidth, m.kad_scale) == (None, 100.0)
+    m = am.AudioMetrics(metrics=["fad", "kad"], kad_bandwidth=2.5, kad_scale=1.0, **kw)
+    assert (m.kad_bandwidth, m.kad_scale) == (2.5, 1.0)
+    with pytest.raises(NotImplementedError, match="kad.*process_group"):
+        am.AudioMetrics(metrics=["fad", "kad"], process_group=object(), **kw)
+    with pytest.raises(NotImplementedError, match="float64"):
+        am.AudioMetrics(metrics=["kad"], n_pca=8, **kw)
+    am.AudioMetrics(metrics=["fad", "kd"], n_pca=8, **kw)              # without "kad" both stay allowed
+
+
+def test_validation_happens_before_any_device_call(am, monkeypatch):
+    from audio_metrics_amd import hip_ops
+
+    def forbidden(*a, **k):
+        raise AssertionError("device call before validation")
+    for name in ("pairwise_select_sq", "mmd_rbf_sums", "as_matrix"):
+        monkeypatch.setattr(hip_ops, name, forbidden)
+
+    def host_set(rows):
+        s = am.AudioMetricsData(True)
+        s._embeddings = rows
+        return s
+    ok = host_set(torch.zeros((10, 8)))
+    with pytest.raises(ValueError, match="store"):
+        am.kernel_audio_distance(am.AudioMetricsData(False), ok)
+    with pytest.raises(ValueError, match="at least 2 rows in the candidate"):
+        am.kernel_audio_distance(host_set(torch.zeros((1, 8))), ok)
+    with pytest.raises(ValueError, match="at least 2 rows in the reference"):
+        am.kernel_audio_distance(ok, host_set(torch.zeros((1, 8))))
+    with pytest.raises(NotImplementedError, match="float64"):
+        am.kernel_audio_distance(ok, host_set(torch.zeros((10, 8), dtype=torch.float64)))
+    with pytest.raises(ValueError, match="feature widths"):
+        am.kernel_audio_distance(ok, host_set(torch.zeros((10, 12))))
+    for bad in (0.0, -1.0, float("nan"), float("inf")):
+        with pytest.raises(ValueError, match="bandwidth"):
+            am.kernel_audio_distance(ok, ok, bandwidth=bad)
+
+
+# ---------------------------------------------------------------------------------------------------- compile-time resources
+@pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"), reason="hipcc not available")
+def test_kad_kernels_use_no_scratch_memory():
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("am_build", os.path.join(ROOT, "audio-metrics_amd", "_build.py"))
+    build = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(build)                                         # the flags the shipped library is built with
+    r = subprocess.run([hipcc, *build.HIPCC_FLAGS, "--cuda-device-only", "-c", "kad.hip", "-o", os.devnull,
+                        "-Rpass-analysis=kernel-resource-usage"], cwd=CSRC, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    usage, name = {}, None
+    for line in r.stderr.splitlines():
+        m = re.search(r"Function Name: (\S+)", line)
+        if m:
+            name = m.group(1)
+            usage[name] = {}
+        for key, short in (("ScratchSize \\[bytes/lane\\]", "scratch"), ("VGPRs", "vgprs"), ("Occupancy \\[waves/SIMD\\]", "occupancy")):
+            m = re.search(r"remark:\s+%s: (\d+)" % key, line)
+            if m and name:
+                usage[name][short] = int(m.group(1))
+    for kernel, count in (("kad_select_kernel", 6), ("kad_mmd_kernel", 2), ("kad_scan_kernel", 3), ("kad_norms_kernel", 1),
+                          ("kad_reduce_kernel", 1)):
+        hits = {n: u for n, u in usage.items() if kernel in n}
+        assert len(hits) == count, (kernel, sorted(usage))
+        for n, u in hits.items():
+            assert u["scratch"] == 0, (n, u)
+            assert u["vgprs"] <= 256 and u["occupancy"] >= 2, (n, u)       # tile kernels: two workgroups of four waves per CU
