@@ -9,6 +9,7 @@ from ._build import build_library, LIB_PATH        # noqa: F401
 from .data import AudioMetricsData, ensure_tensor, ensure_ndarray            # noqa: F401
 from . import metrics                                                         # noqa: F401
 from .metrics.fad import frechet_distance, frechet_distance_inf               # noqa: F401
+from .metrics.fad import frechet_distance_per_group                           # noqa: F401
 from .metrics.kd import kernel_distance, kid_features_to_metric               # noqa: F401
 from .metrics.kad import kernel_audio_distance                                # noqa: F401
 from .metrics.prdc import prdc, nearest_neighbour_distances                   # noqa: F401

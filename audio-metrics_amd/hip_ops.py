@@ -478,6 +478,62 @@ def frechet_batch(mu_x, cov_x, mu_y, cov_y, max_iter=64, tol=1e-13, out=None):
     return [dict(fd=r[0], tr_sqrt=r[1], iters=int(r[2]), resid=r[3], stop=int(r[4])) for r in rec]
 
 
+_GROUPS_MAX = None
+
+
+def frechet_groups_max_rows():
+    global _GROUPS_MAX
+    if _GROUPS_MAX is None:
+        _GROUPS_MAX = int(_lib.load().am_frechet_groups_max_rows())
+    return _GROUPS_MAX
+
+
+def frechet_groups(rows, idx, offsets, mu_y, cov_y, out=None):
+    """Per-group Frechet distances in the dual form (am_frechet_groups_f32 / _f64, by the dtype of rows): group b is the
+    rows rows[idx[offsets[b]:offsets[b + 1]]] (idx: int64 device tensor, or None for the rows in stored order; offsets:
+    B + 1 host integers starting at 0), every group of 1 .. frechet_groups_max_rows() rows, scored against the one
+    reference (mu_y [D], cov_y [D, D]).  Nothing waits for the device: returns (out, check) with out the f64 device tensor
+    [B, 5] of { fd, tr_sqrt, sweeps, residual, stop code } records and check() the one host read of the workspace's flag
+    word, which raises ValueError for an index outside [0, N) (the kernels never dereference it)."""
+    lib = _lib.load()
+    f64 = is_f64(rows)
+    rows = as_rows(rows)
+    n, d = rows.shape
+    mu_y, cov_y = _f64(mu_y, "mu_y"), _f64(cov_y, "cov_y")
+    if mu_y.numel() != d or tuple(cov_y.shape) != (d, d):
+        raise ValueError(f"inconsistent shapes: rows {tuple(rows.shape)}, mu_y {tuple(mu_y.shape)}, cov_y {tuple(cov_y.shape)}")
+    offs = [int(o) for o in offsets]
+    b = len(offs) - 1
+    if b < 1 or offs[0] != 0 or any(offs[i + 1] <= offs[i] for i in range(b)):
+        raise ValueError(f"offsets must start at 0 and increase strictly (got {offs[:4]}{'...' if b > 3 else ''})")
+    dev = _same_device(rows, mu_y, cov_y)
+    if idx is not None:
+        _require_cuda(idx, "idx")
+        idx = idx.to(torch.int64).contiguous()
+        _same_device(rows, idx)
+        if idx.numel() < offs[-1]:
+            raise ValueError(f"idx holds {idx.numel()} entries, offsets name {offs[-1]}")
+    if out is None:
+        out = torch.empty((b, 5), dtype=torch.float64, device=dev)
+    elif out.dtype != torch.float64 or tuple(out.shape) != (b, 5) or not out.is_contiguous() or out.device != dev:
+        raise ValueError("out must be a contiguous float64 [B, 5] tensor on the rows' device")
+    nb = lib.am_frechet_groups_workspace_bytes(offs[-1], b, d)
+    ws = _workspace(nb, dev)
+    host_offs = (ctypes.c_int64 * (b + 1))(*offs)
+    _call(lib, "am_frechet_groups_f64" if f64 else "am_frechet_groups_f32", dev, _ptr(rows), n, _ld64(rows) if f64 else _ld(rows), d,
+          _ptr(idx) if idx is not None else ctypes.c_void_p(None), ctypes.cast(host_offs, ctypes.c_void_p), b, _ptr(mu_y), _ptr(cov_y),
+          _ptr(out), _ptr(ws), nb)
+
+    def check():
+        flag = int(ws[:8].view(torch.int64).item())          # the one host read: 1 + position of an out-of-range index, or 0
+        if flag != 0:
+            pos = flag - 1
+            bad = int(idx[pos].item()) if idx is not None else pos
+            raise ValueError(f"idx[{pos}] = {bad} is outside [0, {n}) (group rows are named by stored-row index)")
+
+    return out, check
+
+
 class FrechetJob:
     """A Frechet solve in flight on a side stream (frechet_async).  Nothing here blocks the host until .result()."""
 

@@ -126,3 +126,115 @@ def frechet_distance_inf(x: AudioMetricsData, y: AudioMetricsData, steps=FAD_INF
     last_info.update(sizes=[int(m) for m in sizes], fads=fads, iters=[r["iters"] for r in res], stops=[r["stop"] for r in res],
                      resids=[r["resid"] for r in res], seed=int(seed))
     return {"fad_inf": intercept, "fad_inf_slope": slope, "fad_inf_r2": r2}
+
+
+# ------------------------------------------------------------------ per-group ("per-song") Frechet distance
+def _group_labels(groups):
+    """The labels as a 1-D integer torch tensor (host or device, as given); no device call."""
+    if isinstance(groups, torch.Tensor):
+        labels = groups
+        if labels.dtype == torch.bool or labels.is_floating_point() or labels.is_complex():
+            raise ValueError(f"groups must hold integer labels, got dtype {labels.dtype}")
+    else:
+        arr = np.asarray(groups)
+        if arr.size and arr.dtype.kind not in "iu":
+            raise ValueError(f"groups must hold integer labels, got dtype {arr.dtype}")
+        if arr.dtype.kind == "u" and arr.size and int(arr.max()) > np.iinfo(np.int64).max:
+            raise ValueError("groups holds a label beyond the int64 range")
+        labels = torch.as_tensor(np.ascontiguousarray(arr.astype(np.int64)))
+    if labels.dim() != 1:
+        raise ValueError(f"groups must be 1-D (one label per stored row), got shape {tuple(labels.shape)}")
+    return labels
+
+
+def frechet_distance_per_group(x: AudioMetricsData, y: AudioMetricsData, groups, device=None):
+    """Frechet distance of every group of x's stored rows, each on its own, against y's full-set statistics (the
+    "individual" / per-song score of the evaluation toolkits).  `groups`: one integer label per stored row of x (numpy or
+    torch, any order, any values).  Groups of up to hip_ops.frechet_groups_max_rows() rows take the dual form - the
+    eigenvalues of the n x n matrix Xc cov_y Xc^T / (n - 1), one library call for all of them, no covariance per group;
+    larger groups take the gathered statistics and the batched Newton-Schulz solve, in chunks of groups.  Returns
+    {"fad_per_group": f64 [B], "group_labels": [B] ascending, "group_sizes": int64 [B]}; last_info carries, per group in
+    label order, "routes" ("dual" / "batch"), "sweeps" (Jacobi sweeps; None on the batch route), "iters" (Newton-Schulz
+    iterations; None on the dual route), "resids" and "stops".  A group whose solve did not end well raises HipLibraryError
+    naming its label: on the dual route any stop code other than 1 (2 = sweep cap, 4 = non-finite input); on the batch
+    route the codes of am_frechet_batch_f64 that are no result - 0 (iteration cap reached) and 4 (non-finite product) -
+    while its other stopping rules (1 converged, 2 trace stalled, 3 zero product) are regular ends there; a non-finite value
+    raises on either route.  The dual form is
+    the dust-free definition for a group with fewer rows than dimensions, so no rank-deficiency warning is raised here."""
+    rows = getattr(x, "embeddings", None)
+    n = int(rows.shape[0]) if rows is not None else 0
+    if rows is None or n == 0:
+        raise ValueError(f"frechet_distance_per_group scores the stored rows of its first argument, which keeps none "
+                         f"(store_embeddings={getattr(x, 'store_embeddings', None)})")
+    labels = _group_labels(groups)
+    if labels.numel() == 0:
+        raise ValueError("groups is empty")
+    if labels.numel() != n:
+        raise ValueError(f"groups holds {labels.numel()} labels for {n} stored rows (one label per row)")
+    d = int(rows.shape[1])
+    d_y = int(ensure_tensor(y.mean).numel())
+    if d_y != d:
+        raise ValueError(f"feature widths differ: the rows have {d} columns, the reference statistics {d_y}")
+    if device is None:
+        device = rows.device if rows.is_cuda else None
+    if device is None:
+        from ..data import default_device
+        device = default_device()
+    device = torch.device(device)
+    rows = ops.as_rows(rows.to(device))
+    mu_y, cov_y = (ensure_tensor(t).to(device, torch.float64) for t in (y.mean, y.cov))
+    mu_y = mu_y.reshape(-1)
+    labels = labels.to(device, torch.int64)
+    sorted_labels, order = torch.sort(labels, stable=True)
+    uniq, counts = torch.unique_consecutive(sorted_labels, return_counts=True)
+    host = torch.stack([uniq, counts]).cpu().numpy()                       # the one read-back in front of the kernels
+    group_labels, sizes = host[0].copy(), host[1].astype(np.int64)
+    nb = len(sizes)
+    cap = ops.frechet_groups_max_rows()
+    small = sizes <= cap
+    if small.all():
+        idx_small, idx_large = order, None
+    else:
+        on_dev = torch.repeat_interleave(torch.as_tensor(small, device=device), counts)
+        idx_small, idx_large = order[on_dev], order[~on_dev]
+    fads = np.empty(nb, dtype=np.float64)
+    steps, resids, stops = np.zeros(nb, dtype=np.int64), np.zeros(nb), np.zeros(nb, dtype=np.int64)
+    rec_small = check_small = None
+    if small.any():
+        offs = np.concatenate([[0], np.cumsum(sizes[small])])
+        rec_small, check_small = ops.frechet_groups(rows, idx_small, offs.tolist(), mu_y, cov_y)
+    large = np.flatnonzero(~small)
+    if len(large):
+        per_set = max(int(ops._lib.load().am_frechet_batch_workspace_bytes(1, d)), 1)
+        chunk = max(1, min(65535, ops.FRECHET_BATCH_WS_CAP // per_set))
+        offs = np.concatenate([[0], np.cumsum(sizes[large])])
+        for c0 in range(0, len(large), chunk):
+            c1 = min(len(large), c0 + chunk)
+            means, covs, check = ops.stats_gather(rows, idx_large[offs[c0]:offs[c1]], (offs[c0:c1 + 1] - offs[c0]).tolist(),
+                                                  defer_check=True)
+            rec_large = torch.empty((c1 - c0, 5), dtype=torch.float64, device=device)
+            try:
+                ops.frechet_batch(means, covs, mu_y, cov_y, NS_MAX_ITER, NS_TOL, out=rec_large)
+            except ops._lib.HipLibraryError:                  # a stop code 4 in the chunk: every record is written all the same,
+                pass                                          # and the group is named by its label below
+            check()
+            rec = rec_large.cpu().numpy()
+            where = large[c0:c1]
+            fads[where], steps[where], resids[where], stops[where] = rec[:, 0], rec[:, 2].astype(np.int64), rec[:, 3], rec[:, 4].astype(np.int64)
+    if rec_small is not None:
+        rec = rec_small.cpu().numpy()
+        check_small()
+        where = np.flatnonzero(small)
+        fads[where], steps[where], resids[where], stops[where] = rec[:, 0], rec[:, 2].astype(np.int64), rec[:, 3], rec[:, 4].astype(np.int64)
+    routes = ["dual" if s else "batch" for s in small]
+    last_info.clear()
+    last_info.update(sweeps=[int(v) if s else None for v, s in zip(steps, small)],
+                     iters=[None if s else int(v) for v, s in zip(steps, small)], resids=resids.tolist(), stops=stops.tolist(), routes=routes,
+                     group_labels=group_labels.tolist(), group_sizes=sizes.tolist())
+    bad = [g for g in range(nb) if (stops[g] != 1 if small[g] else stops[g] in (0, 4)) or not np.isfinite(fads[g])]
+    if bad:
+        g = bad[0]
+        raise ops._lib.HipLibraryError(f"frechet_distance_per_group: group with label {int(group_labels[g])} ({int(sizes[g])} rows, "
+                                       f"{routes[g]} route) ended with stop code {int(stops[g])} "
+                                       f"(labels of all such groups: {[int(group_labels[i]) for i in bad]})")
+    return {"fad_per_group": fads, "group_labels": group_labels, "group_sizes": sizes}

@@ -176,6 +176,38 @@ int am_frechet_batch_f64(const double* mu_x, const double* cov_x,
                          const double* mu_y, const double* cov_y, int64_t y_stride_sets,
                          int B, int D, int max_iter, double tol, double* out_dev,
                          void* ws, size_t ws_bytes, am_stream_t stream);
+/* Per-group ("per-song") Frechet distance in the dual form: B small groups of rows of ONE stored matrix, each scored on its
+ * own against one reference (mu_y, cov_y).  Group b is the rows X[idx[offsets[b] + j]], j < n_b; idx == NULL names the rows
+ * in stored order (group b = rows offsets[b] .. offsets[b + 1] - 1).  With Xc the centred rows of a group, the non-zero
+ * eigenvalues of cov_x cov_y are those of the symmetric n_b x n_b matrix M = Xc cov_y Xc^T / (n_b - 1), so
+ *   fd = |mu_x - mu_y|^2 + |Xc|_F^2 / (n_b - 1) + tr cov_y - 2 sum_i sqrt(lambda_i(M))
+ * and no D x D matrix is formed per group: the workspace is 2 * n_total * D doubles (Xc and Z = Xc cov_y) plus 32 bytes per
+ * group.  The number of launches does not depend on B; the call is asynchronous and deterministic.
+ *   idx      DEVICE or NULL                          offsets  HOST, B + 1 entries, offsets[0] == 0
+ *   mu_y     DEVICE [D], cov_y DEVICE [D][D] (symmetric)
+ *   out_dev  DEVICE [B][5]: { fd, tr_sqrt, sweeps, residual, stop code }; stop code 1 = converged, 2 = sweep cap reached,
+ *            4 = non-finite input; residual = off-diagonal norm / |M|_F at the end
+ * Every group needs 1 <= n_b <= am_frechet_groups_max_rows() (128: a 128 x 128 f64 matrix is 128 KiB of the CU's 160 KiB
+ * LDS), else AM_ERR_BAD_SHAPE naming the group.  Arithmetic, all in f64 for both entry points: float32 rows are converted on
+ * load (exact), so am_frechet_groups_f32 returns the SAME BITS as am_frechet_groups_f64 on the same values; column means are
+ * added in list order; rows are centred in f64; Z and M come from v_mfma_f64_16x16x4_f64, the upper triangle of M is computed
+ * and mirrored; the eigenvalues come from a cyclic Jacobi in LDS (round-robin ordering, eigenvalues only) that runs until
+ * the off-diagonal norm is <= 2^-52 |M|_F or 30 sweeps have passed; eigenvalues <= 4 n_b 2^-52 lambda_max count as zero (a
+ * centred group always has one exact null vector, duplicate rows add more); the square roots are added in index order.
+ * n_b == 1: fd = |dmu|^2 + tr cov_y, tr_sqrt = 0, stop code 1 (one row has zero covariance).
+ * An index outside [0, N) is never dereferenced: the row counts as zeros and the FIRST 8 BYTES OF `ws` receive 1 + the
+ * largest position in idx that held such an index (0 = all valid), as am_stats_gather_* reports it; the records of the other
+ * groups are unaffected.  X: the alignment, ld and 4 GiB rules of am_stats_gather_*. */
+int am_frechet_groups_max_rows(void);
+size_t am_frechet_groups_workspace_bytes(int64_t n_total, int B, int D);
+int am_frechet_groups_f32(const float* X, int64_t N, int64_t ld, int D,
+                          const int64_t* idx, const int64_t* offsets, int B,
+                          const double* mu_y, const double* cov_y,
+                          double* out_dev, void* ws, size_t ws_bytes, am_stream_t stream);
+int am_frechet_groups_f64(const double* X, int64_t N, int64_t ld, int D,
+                          const int64_t* idx, const int64_t* offsets, int B,
+                          const double* mu_y, const double* cov_y,
+                          double* out_dev, void* ws, size_t ws_bytes, am_stream_t stream);
 
 /* A11 APA scalar combination (host arithmetic)  reference: apa.py:22-32 */
 double am_apa_f64(double d_y_x, double d_y_xp, double d_x_xp);
