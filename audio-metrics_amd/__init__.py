@@ -12,6 +12,7 @@ from .metrics.fad import frechet_distance, frechet_distance_inf               # 
 from .metrics.fad import frechet_distance_per_group                           # noqa: F401
 from .metrics.kd import kernel_distance, kid_features_to_metric               # noqa: F401
 from .metrics.kad import kernel_audio_distance                                # noqa: F401
+from .metrics.kad import kernel_audio_distance_per_group                      # noqa: F401
 from .metrics.prdc import prdc, nearest_neighbour_distances                   # noqa: F401
 from .metrics.apa import apa, apa_compute_d_x_xp                              # noqa: F401
 

@@ -21,6 +21,7 @@
 //   diagonal dropped) and Sxy (all tiles) of K = exp(-d2 gamma) in f64.  One f64 partial per workgroup, written to its own
 //   slot and summed by a one-workgroup kernel in a fixed order: identical inputs give identical bits.
 #include "am_common.h"
+#include "kad_common.h"
 #include "pairwise_common.h"
 #include <algorithm>
 
@@ -29,7 +30,6 @@ namespace am {
 constexpr int KAD_BINS = 2048;                       // 11-bit first digit; the 10-bit digits use the lower half
 constexpr int KAD_PASSES = 3;
 constexpr int KAD_AGG_ROUNDS = 3;
-constexpr int KAD_MAX_CHUNK = 16;                    // Q tiles per workgroup
 // 73 728 B of staging slabs + 8 192 B of counters = 81 920 B: exactly two workgroups in a CU's 160 KiB
 constexpr size_t KAD_SELECT_LDS_BYTES = ENGINE_LDS_FLOATS * sizeof(float) + KAD_BINS * sizeof(unsigned);
 constexpr size_t KAD_MMD_LDS_BYTES = ENGINE_LDS_FLOATS * sizeof(float);
@@ -195,15 +195,20 @@ __global__ void __launch_bounds__(256) kad_scan_kernel(const unsigned long long*
     }
 }
 
-// Q tiles per workgroup: enough workgroups to fill the chip at small sizes, few global flushes / partials at large ones;
-// grid.y must stay below 65536
-static int kad_chunk(int64_t tiles_total, int64_t q_tiles) {
+// Q tiles per workgroup (kad_common.h)
+int kad_chunk(int64_t tiles_total, int64_t q_tiles) {
     int64_t ch = std::min<int64_t>(KAD_MAX_CHUNK, std::max<int64_t>(1, tiles_total / 2048));
     while (ceil_div(q_tiles, ch) > 65535) ch *= 2;
     return (int)ch;
 }
 
-static bool kad_too_large(int64_t N, int64_t ld) { return (uint64_t)N * (uint64_t)ld * 4u >= 0xffffffffull; }
+bool kad_too_large(int64_t N, int64_t ld) { return (uint64_t)N * (uint64_t)ld * 4u >= 0xffffffffull; }
+
+int launch_kad_norms(const float* X, int64_t ld, int D, int64_t N, double* out, hipStream_t st) {
+    hipLaunchKernelGGL(kad_norms_kernel, dim3((unsigned)ceil_div(N, 4)), dim3(256), 0, st, X, ld, D, N, out);
+    AM_LAUNCH_CHECK();
+    return AM_OK;
+}
 
 static size_t select_ws(int64_t N) {
     Carver c(nullptr, 0);

@@ -695,6 +695,59 @@ def mmd_rbf_sums(x, y, bw2=None, gamma=None, blocks=7, out=None):
     return out
 
 
+def mmd_rbf_group_sums(x, idx, offsets, y, bw2=None, gamma=None, rows=False):
+    """Per-group Gaussian kernel sums in one library call (am_mmd_rbf_groups_f32): group b is the rows
+    x[idx[offsets[b]:offsets[b + 1]]] (idx: int64 device tensor, or None for the rows in stored order; offsets: B + 1 host
+    integers starting at 0, strictly increasing; any group size), each against the whole reference y.  `bw2` / `gamma` as
+    for mmd_rbf_sums.  Nothing waits for the device: returns (out_groups, check), or (out_groups, out_rows, check) with
+    rows=True - out_groups the f64 device tensor [B, 2] of {Sxx_b, Sxy_b} (Sxx_b over the ordered pairs i != j inside the
+    group, Sxy_b over all n_b N2 pairs), out_rows the f64 device tensor [n_total, 2] of the row sums {w_i, c_i} in LIST
+    order, and check() the one host read of the workspace's flag word, which raises ValueError for an index outside
+    [0, N1) (the kernels never dereference it)."""
+    lib = _lib.load()
+    if is_f64(x) or is_f64(y):
+        raise NotImplementedError("mmd_rbf_group_sums takes float32 rows (the float64 matrix-core form is not implemented)")
+    if (bw2 is None) == (gamma is None):
+        raise ValueError("exactly one of bw2 (device scalar) and gamma (number) must be given")
+    x, y = as_matrix(x, "x"), as_matrix(y, "y")
+    dev = _same_device(x, y)
+    n, d = x.shape
+    if d != y.shape[1]:
+        raise ValueError(f"feature widths differ: {d} and {y.shape[1]}")
+    offs = [int(o) for o in offsets]
+    b = len(offs) - 1
+    if b < 1 or offs[0] != 0 or any(offs[i + 1] <= offs[i] for i in range(b)):
+        raise ValueError(f"offsets must start at 0 and increase strictly (got {offs[:4]}{'...' if b > 3 else ''})")
+    if idx is not None:
+        _require_cuda(idx, "idx")
+        idx = idx.to(torch.int64).contiguous()
+        _same_device(x, idx)
+        if idx.numel() < offs[-1]:
+            raise ValueError(f"idx holds {idx.numel()} entries, offsets name {offs[-1]}")
+    if bw2 is not None:
+        _require_cuda(bw2, "bw2")
+        if bw2.dtype != torch.float32 or bw2.numel() != 1:
+            raise ValueError("bw2 must be a float32 device scalar")
+    out_groups = torch.empty((b, 2), dtype=torch.float64, device=dev)
+    out_rows = torch.empty((offs[-1], 2), dtype=torch.float64, device=dev) if rows else None
+    nb = lib.am_mmd_rbf_groups_workspace_bytes(offs[-1], b, y.shape[0], d)
+    ws = _workspace(nb, dev)
+    host_offs = (ctypes.c_int64 * (b + 1))(*offs)
+    null = ctypes.c_void_p(None)
+    _call(lib, "am_mmd_rbf_groups_f32", dev, _ptr(x), n, _ld(x), _ptr(idx) if idx is not None else null,
+          ctypes.cast(host_offs, ctypes.c_void_p), b, _ptr(y), y.shape[0], _ld(y), d, _ptr(bw2) if bw2 is not None else null,
+          0.0 if gamma is None else float(gamma), _ptr(out_groups), _ptr(out_rows) if rows else null, _ptr(ws), nb)
+
+    def check():
+        flag = int(ws[:8].view(torch.int64).item())          # the one host read: 1 + position of an out-of-range index, or 0
+        if flag != 0:
+            pos = flag - 1
+            bad = int(idx[pos].item()) if idx is not None else pos
+            raise ValueError(f"idx[{pos}] = {bad} is outside [0, {n}) (group rows are named by stored-row index)")
+
+    return (out_groups, out_rows, check) if rows else (out_groups, check)
+
+
 # ------------------------------------------------------------------ PRDC
 class PreparedSet:
     """What every PRDC entry point derives from a set before its tile kernels run - squared row norms, their maximum, the

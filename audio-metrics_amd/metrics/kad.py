@@ -11,11 +11,14 @@ the reason the field adopted it - no bias in the sample size.  The reference-sid
 the reference set alone and is kept on it: a big cached reference against a small candidate set costs the cross block."""
 import math
 import struct
+import warnings
 
+import numpy as np
 import torch
 
 from .. import hip_ops as ops
 from ..data import AudioMetricsData
+from .fad import _group_labels
 
 KAD_SCALE = 100.0
 CACHE_ATTR = "_kad_cache"         # on the reference AudioMetricsData; NOT part of serialize(): the file layout stays as it is
@@ -103,6 +106,102 @@ def kernel_audio_distance(x: AudioMetricsData, y: AudioMetricsData, bandwidth=No
         cache.syy[_gamma_bits(gamma)] = syy
     mmd2 = sxx / (n * (n - 1.0)) + syy_v / (m * (m - 1.0)) - 2.0 * sxy / (float(n) * m)
     return {"kad": float(scale) * mmd2, "kad_mmd2": mmd2, "kad_bandwidth": bw}
+
+
+def combine_group_sums(sxx, sxy, sizes, syy, m, scale=KAD_SCALE):
+    """(kad_per_group, mmd2_per_group) from the per-group kernel sums - host arithmetic, float64 numpy:
+        mmd2_b = Sxx_b / (n_b (n_b - 1)) + Syy / (m (m - 1)) - 2 Sxy_b / (n_b m).
+    A group of one row has no unbiased estimate: its value is NaN, and ONE RuntimeWarning per call says how many such groups
+    there are.  A NaN sum (a non-finite row in that group) stays the NaN of that group alone."""
+    sxx, sxy = np.asarray(sxx, dtype=np.float64), np.asarray(sxy, dtype=np.float64)
+    n = np.asarray(sizes, dtype=np.float64)
+    single = n < 2
+    pairs = np.where(single, np.nan, n * (n - 1.0))
+    mmd2 = sxx / pairs + float(syy) / (m * (m - 1.0)) - 2.0 * sxy / (n * float(m))
+    if single.any():
+        warnings.warn(f"kernel_audio_distance_per_group: {int(single.sum())} of {len(n)} groups hold a single row and have no "
+                      "unbiased MMD^2 (it divides by n (n - 1)); their value is NaN", RuntimeWarning, stacklevel=3)
+    return float(scale) * mmd2, mmd2
+
+
+def kernel_audio_distance_per_group(x: AudioMetricsData, y: AudioMetricsData, groups, bandwidth=None, scale=KAD_SCALE,
+                                    return_rows=False):
+    """KAD of every group of x's stored rows, each on its own, against the whole reference set y (the per-song score: the
+    unbiased MMD^2 has no bias in the group size, so groups of different sizes compare).  `groups`: one integer label per
+    stored row of x (numpy or torch, any order, any values).  One library call for all groups (ops.mmd_rbf_group_sums: the
+    Gram work of one cross block); the bandwidth and Syy come from - and go into - the reference-side cache that
+    kernel_audio_distance uses.  Returns {"kad_per_group": f64 [B], "kad_mmd2_per_group": f64 [B], "group_labels": [B]
+    ascending, "group_sizes": int64 [B], "kad_bandwidth": float}; return_rows=True adds "row_cross_mean": f64 [n] in STORED
+    row order, c_i / m = the reference's kernel density at each candidate row.  A group of one row gets NaN and the call
+    one RuntimeWarning."""
+    rows = getattr(x, "embeddings", None)
+    n = int(rows.shape[0]) if rows is not None else 0
+    if rows is None or n == 0:
+        raise ValueError(f"kernel_audio_distance_per_group scores the stored rows of its candidate set, which keeps none "
+                         f"(store_embeddings={getattr(x, 'store_embeddings', None)})")
+    labels = _group_labels(groups)
+    if labels.numel() == 0:
+        raise ValueError("groups is empty")
+    if labels.numel() != n:
+        raise ValueError(f"groups holds {labels.numel()} labels for {n} stored rows (one label per row)")
+    ey = _rows_of(y, "reference")
+    if rows.dtype == torch.float64:
+        raise NotImplementedError("kernel_audio_distance_per_group: the candidate set holds float64 rows; the float64 "
+                                  "matrix-core form of the kernel sums is not implemented")
+    if rows.shape[1] != ey.shape[1]:
+        raise ValueError(f"feature widths differ: {rows.shape[1]} and {ey.shape[1]}")
+    gamma = None
+    if bandwidth is not None:
+        bw = float(bandwidth)
+        if not math.isfinite(bw) or bw <= 0.0:
+            raise ValueError(f"bandwidth={bandwidth!r} must be a finite positive number")
+        gamma = 1.0 / (2.0 * bw * bw)
+    m = int(ey.shape[0])
+    labels = labels.to(rows.device, torch.int64)
+    sorted_labels, order = torch.sort(labels, stable=True)
+    uniq, counts = torch.unique_consecutive(sorted_labels, return_counts=True)
+    host = torch.stack([uniq, counts]).cpu().numpy()                       # the one read-back in front of the kernels
+    group_labels, sizes = host[0].copy(), host[1].astype(np.int64)
+    offs = np.concatenate([[0], np.cumsum(sizes)]).tolist()
+    cache = reference_cache(y)
+    bw2_dev = None
+    if gamma is None:
+        if cache.bw2 is None:
+            cache.bw2 = ops.pairwise_select_sq(ey)
+        bw2_dev = cache.bw2
+        if cache.bw2_host is not None:                     # the bits the device forms from the same float32: 0.5 / (double)bw2
+            _check_bandwidth(cache.bw2_host)
+            gamma = 0.5 / cache.bw2_host
+    width = {"bw2": bw2_dev} if bw2_dev is not None else {"gamma": gamma}
+    syy = cache.syy.get(_gamma_bits(gamma)) if gamma is not None else None
+    fresh_syy = syy is None
+    if fresh_syy:
+        syy = ops.mmd_rbf_sums(ey, ey, blocks=ops.MMD_YY, **width)[1].clone()
+    res = ops.mmd_rbf_group_sums(rows, order, offs, ey, rows=return_rows, **width)
+    out_groups, check = res[0], res[-1]
+    tail = bw2_dev.to(torch.float64) if bw2_dev is not None else torch.zeros((), dtype=torch.float64, device=out_groups.device)
+    parts = [out_groups.reshape(-1), torch.stack([syy, tail])]
+    if return_rows:
+        stored = torch.empty(n, dtype=torch.float64, device=out_groups.device)
+        stored[order] = res[1][:, 1] / float(m)            # list order -> stored order
+        parts.append(stored)
+    flat = torch.cat(parts).cpu().numpy()                   # the one read-back of results
+    check()
+    nb = len(sizes)
+    syy_v, bw2_v = float(flat[2 * nb]), float(flat[2 * nb + 1])
+    if bw2_dev is not None:
+        cache.bw2_host = bw2_v
+        _check_bandwidth(bw2_v)
+        gamma = 0.5 / bw2_v
+        bw = math.sqrt(bw2_v)
+    if fresh_syy:
+        cache.syy[_gamma_bits(gamma)] = syy
+    sums = flat[:2 * nb].reshape(nb, 2)
+    kad, mmd2 = combine_group_sums(sums[:, 0], sums[:, 1], sizes, syy_v, m, scale)
+    out = {"kad_per_group": kad, "kad_mmd2_per_group": mmd2, "group_labels": group_labels, "group_sizes": sizes, "kad_bandwidth": bw}
+    if return_rows:
+        out["row_cross_mean"] = flat[2 * nb + 2:].copy()
+    return out
 
 
 def _check_bandwidth(bw2):

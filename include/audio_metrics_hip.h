@@ -290,6 +290,40 @@ int am_mmd_rbf_f32(const float* X, int64_t N1, int64_t ldx,
                    double* out_sums, void* ws, size_t ws_bytes, am_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Per-group Kernel Audio Distance (csrc/kad_groups.hip, f32 tile engine): the Gaussian kernel sums of B groups of rows of
+ * one stored matrix X, each group on its own against the one reference set Y, in ONE call whose number of launches does not
+ * depend on B.  Group b is the rows X[idx[offsets[b] + j]], j < n_b; idx == NULL names the rows in stored order.  With
+ * k(a, b) = exp(-d2(a, b) gamma) in the arithmetic of am_mmd_rbf_f32 (f64 norms, f32 matrix-core dot product, exp in f64):
+ *   row sums   c_i = sum_j k(x_i, y_j) over all N2 reference rows,   w_i = sum_{j in group(i), j != i} k(x_i, x_j)
+ *   out_groups[b] = { Sxx_b = sum_{i in b} w_i,  Sxy_b = sum_{i in b} c_i }          (DEVICE [B][2])
+ *   out_rows[p]   = { w_p, c_p } for list position p, i.e. in LIST order            (DEVICE [n_total][2], or NULL)
+ *   unbiased MMD^2 of group b = Sxx_b / (n_b (n_b - 1)) + Syy / (N2 (N2 - 1)) - 2 Sxy_b / (n_b N2)   (left to the caller;
+ *   Syy from am_mmd_rbf_f32(blocks = AM_MMD_YY); n_b == 1 has no unbiased estimate, its Sxx_b is 0).
+ * The cross pass does the Gram work of one Sxy pass of am_mmd_rbf_f32 with the candidate rows gathered through the list (no
+ * gathered copy is made); the within pass covers, per 128-position tile, the tiles of the tile's own groups, masked to equal
+ * groups.  A lane keeps one f64 running sum per candidate row; a workgroup's sums are combined in a fixed order and written
+ * to a slot of its own, a row's chunks are added in chunk order and a group's rows by strided sums and a tree: no atomics,
+ * two calls on the same input give the same bits, and the result depends on the list order only - not on where the rows
+ * are stored (idx == NULL on a group-ordered store and a permutation idx into a shuffled store give the same bits).
+ *   idx      DEVICE or NULL                          offsets  HOST, B + 1 entries, offsets[0] == 0, strictly increasing
+ *   bw2_dev  DEVICE float or NULL: gamma = 0.5 / (double)*bw2_dev is formed on the device and `gamma` is ignored
+ * Any n_b >= 1 is allowed, with no upper bound (a group may span many tiles); n_total = offsets[B] < 2^30.
+ * An index outside [0, N1) is never dereferenced: the row counts as zeros and the FIRST 8 BYTES OF `ws` receive 1 + the
+ * largest position in idx that held such an index (0 = all valid), as am_stats_gather_* reports it; the records of the other
+ * groups are unaffected.  A non-finite candidate row makes the sums of its own group NaN and touches no other group; a
+ * non-finite reference row makes every Sxy_b NaN.  X, Y: the alignment, ld and 4 GiB rules of am_mmd_rbf_f32; N2 >= 2.
+ * Everything is validated before the first HIP call (AM_ERR_BAD_ARG / AM_ERR_BAD_SHAPE name the argument, AM_ERR_WORKSPACE
+ * the size wanted); the call is asynchronous.
+ * ------------------------------------------------------------------------- */
+size_t am_mmd_rbf_groups_workspace_bytes(int64_t n_total, int B, int64_t N2, int D);
+int am_mmd_rbf_groups_f32(const float* X, int64_t N1, int64_t ldx,
+                          const int64_t* idx, const int64_t* offsets, int B,
+                          const float* Y, int64_t N2, int64_t ldy, int D,
+                          const float* bw2_dev, double gamma,
+                          double* out_groups, double* out_rows,
+                          void* ws, size_t ws_bytes, am_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * A9  k-NN radii                                reference: prdc.py:4-14, data.py:60-66
  *   out_r[i] = (k+1)-th smallest Euclidean distance from row i of X to the M
  *   rows of Y (Y == X for the reference's self-distance use; a multi-GPU
