@@ -817,6 +817,47 @@ def knn_radii(x, k, columns=None, prepared=None):
     return out
 
 
+KNN_SEARCH_MAX_K = 32
+
+
+def knn_search(x, y, k, self_offset=None, squared=False):
+    """The k nearest rows of y for every row of x (am_knn_search_f32): (dist float32 [N, k] ascending, idx int64 [N, k]) as
+    device tensors, stream-ordered, nothing waits for the device.  Squared distances have the bits of the exact k-NN kernel
+    (column k of a (k + 1)-search is knn_radii(x, k, columns=y)); ties go to the smallest row index of y; `self_offset`:
+    column i + self_offset is skipped for row i (0 for x searched against itself, the shard's first row for a row shard),
+    by index - duplicate rows stay neighbours.  Missing neighbours (fewer than k finite candidates) are (+inf, -1)."""
+    if is_f64(x) or is_f64(y):
+        raise NotImplementedError("knn_search takes float32 rows (the float64 matrix-core form is not implemented)")
+    k = int(k)
+    if not 1 <= k <= KNN_SEARCH_MAX_K:
+        raise ValueError(f"k={k} must be in 1 .. {KNN_SEARCH_MAX_K}")
+    if x.dim() != 2 or y.dim() != 2:
+        raise ValueError(f"x and y must be 2-D, got shapes {tuple(x.shape)} and {tuple(y.shape)}")
+    if x.shape[1] != y.shape[1]:
+        raise ValueError(f"feature widths differ: {x.shape[1]} and {y.shape[1]}")
+    if x.shape[0] < 1 or y.shape[0] < 1:
+        raise ValueError(f"knn_search needs rows on both sides (got {x.shape[0]} and {y.shape[0]})")
+    lib = _lib.load()
+    same = x is y
+    x = as_matrix(x, "x")
+    y = x if same else as_matrix(y, "y")
+    dev = _same_device(x, y)
+    n, d = x.shape
+    m = y.shape[0]
+    dist = torch.empty((n, k), dtype=torch.float32, device=dev)
+    idx = torch.empty((n, k), dtype=torch.int64, device=dev)
+    nb = lib.am_knn_search_workspace_bytes(n, m, d, k)
+    ws = _workspace(nb, dev)
+    _call(lib, "am_knn_search_f32", dev, _ptr(x), n, _ld(x), _ptr(y), m, _ld(y), d, k,
+          -1 if self_offset is None else int(self_offset), 1 if squared else 0, _ptr(dist), _ptr(idx), _ptr(ws), nb)
+    return dist, idx
+
+
+def knn_search_chunks(n, m, d, k):
+    """Column chunks the search's plan cuts the rows of y into (am_knn_search_chunks; tests and tools)."""
+    return int(_lib.load().am_knn_search_chunks(int(n), int(m), int(d), int(k)))
+
+
 # ---- partitioned symmetric k-NN (multi-GPU, every rank holds the full set) ----
 def knn_path(n, m, d, k, self_distance=True):
     """0 exact general kernel, 1 exact symmetric kernel, 2 / 3 f16 filter + exact verification (128 / 256-row engine)."""

@@ -345,6 +345,31 @@ int am_knn_radii_f32(const float* X, int64_t N, int64_t ldx,
                      float* out_r, void* ws, size_t ws_bytes, am_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * k-nearest-neighbour SEARCH (csrc/knn_search.hip, f32 tile engine)          no counterpart in the reference
+ *   For every row i of X the k nearest rows of Y: out_dist[i * k + s] = the s-th smallest distance (ascending),
+ *   out_idx[i * k + s] = the row of Y it belongs to (int64).  The radii above answer "how far"; this answers "which
+ *   rows" - memorisation audits, per-sample inspection, nearest-neighbour ratio tests - without an N x M matrix.
+ *   Arithmetic of a pair: exactly that of the exact k-NN kernel,  d2 = max(fmaf(-2, <x, y>, |x|^2 + |y|^2), 0)  in f32 with
+ *   the same row norms and inner order, so every squared distance has the bits am_knn_radii_f32 works with:
+ *   column k of a (k + 1)-search equals the radius of nearest_k = k bit for bit.  squared != 0: d2 itself; else sqrt_rn(d2).
+ *   Order: by distance, ties by the SMALLEST row index of Y (one unsigned compare on the 64-bit key
+ *   bits(d2) << 32 | column) - independent of chunking and launch geometry: two calls return the same bits.
+ *   self_offset >= 0: column i + self_offset is skipped for row i (X a row shard of Y starting at row self_offset;
+ *   0 for X == Y).  Exclusion is by INDEX, not by a zero distance: duplicates of a row remain its neighbours.
+ *   self_offset < 0: nothing is skipped.
+ *   Fewer than k finite candidates (M < k, M - 1 < k with exclusion, rows with non-finite elements - a NaN distance
+ *   counts as +inf, as for the radii): the trailing entries are distance +inf, index -1.
+ *   1 <= k <= 32 (else AM_ERR_BAD_SHAPE); M < 2^32 - 1; X, Y as for am_knn_radii_f32 (16-byte aligned, ld % 4 == 0,
+ *   ld >= D).  Workspace: the row norms and uint64 [am_knn_search_chunks][N][8 / 16 / 32] partial lists.  Everything is
+ *   validated before the first HIP call; the call is asynchronous.
+ * ------------------------------------------------------------------------- */
+size_t am_knn_search_workspace_bytes(int64_t N, int64_t M, int D, int k);
+int am_knn_search_chunks(int64_t N, int64_t M, int D, int k);      /* column chunks the plan uses (tests, tools) */
+int am_knn_search_f32(const float* X, int64_t N, int64_t ldx, const float* Y, int64_t M, int64_t ldy, int D, int k,
+                      int64_t self_offset, int squared, float* out_dist, int64_t* out_idx,
+                      void* ws, size_t ws_bytes, am_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * A9, partitioned form for one-process-per-GPU callers that all hold the FULL set X.
  * The self-distance matrix is bitwise symmetric, so only half of the tile pairs are multiplied
  * (csrc/pairwise.hip, knn_sym_kernel); rank `part` of `nparts` owns a contiguous range of the 128-row blocks.
