@@ -17,6 +17,7 @@
 //                              mirrored.  Three instantiations (up to 32, 64, 128 rows) so that small groups share a CU.
 // Every reduction runs in a fixed order: the call is deterministic.
 #include "am_common.h"
+#include "groups_common.h"
 
 namespace am {
 
@@ -348,17 +349,13 @@ __global__ void __launch_bounds__(256) fg_solve_kernel(const double* __restrict_
 
 // ---------------------------------------------------------------- host side
 struct GroupsBuffers {
-    unsigned long long* flag;      // first 8 bytes of the workspace
-    int64_t* offs;
+    GroupHead head;
     double *stats, *xc, *z;
 };
 
 static bool carve_groups(Carver& c, int64_t n_total, int B, int D, GroupsBuffers& g) {
-    // one carve-out for the small pieces: flag word, B + 1 offsets, 3 scalars per group
-    char* head = c.take<char>(8 + ((size_t)B + 1) * 8 + (size_t)B * 24);
-    g.flag = reinterpret_cast<unsigned long long*>(head);
-    g.offs = reinterpret_cast<int64_t*>(head ? head + 8 : nullptr);
-    g.stats = reinterpret_cast<double*>(head ? head + 8 + ((size_t)B + 1) * 8 : nullptr);
+    g.head = carve_group_head(c, B, (size_t)B * 24);           // the tail: 3 scalars per group
+    g.stats = reinterpret_cast<double*>(g.head.tail);
     g.xc = c.take<double>(2 * (size_t)n_total * D);
     g.z = g.xc ? g.xc + (size_t)n_total * D : nullptr;
     return c.ok();
@@ -370,51 +367,41 @@ static int frechet_groups(const T* X, int64_t N, int64_t ld, int D, const int64_
     constexpr bool F64 = sizeof(T) == 8;
     AM_REQUIRE(X && offsets && mu_y && cov_y && out, AM_ERR_BAD_ARG, "null pointer");
     AM_REQUIRE(N >= 1 && D >= 1 && B >= 1, AM_ERR_BAD_SHAPE, "X has shape %lld x %d, B=%d (all must be >= 1)", (long long)N, D, B);
-    if (F64) {
-        AM_REQUIRE(D <= 8192 && ld >= D, AM_ERR_BAD_ARG, "float64 rows: D=%d (<= 8192), ld=%lld (>= D)", D, (long long)ld);
-    } else {
-        AM_REQUIRE(aligned16(X) && ld % 4 == 0 && ld >= D, AM_ERR_BAD_ARG,
-                   "X must be 16-byte aligned with ld %% 4 == 0 and ld >= D (ld=%lld, D=%d)", (long long)ld, D);
-        AM_REQUIRE(N * ld < ((int64_t)1 << 30), AM_ERR_BAD_SHAPE,
-                   "float32 rows follow the rules of the gathered statistics: %lld x %lld floats is 4 GiB or more", (long long)N,
-                   (long long)ld);
-    }
-    AM_REQUIRE(offsets[0] == 0, AM_ERR_BAD_ARG, "offsets[0]=%lld, must be 0", (long long)offsets[0]);
-    bool cls[3] = {false, false, false};
+    AM_TRY(check_group_rows(X, N, ld, D));
+    int64_t n_total;
+    AM_TRY(check_group_offsets(offsets, B, FG_MAX_ROWS, &n_total));
+    AM_TRY(check_stored_rows(idx, n_total, N));
+    bool cls[3] = {false, false, false};                       // which of the three solve sizes the groups need
     for (int b = 0; b < B; ++b) {
         const int64_t n = offsets[b + 1] - offsets[b];
-        AM_REQUIRE(n >= 1 && n <= FG_MAX_ROWS, AM_ERR_BAD_SHAPE, "group %d has %lld rows (1 <= rows <= %d)", b, (long long)n, FG_MAX_ROWS);
         cls[n <= 32 ? 0 : n <= 64 ? 1 : 2] = true;
     }
-    const int64_t n_total = offsets[B];
-    AM_REQUIRE(idx || n_total <= N, AM_ERR_BAD_SHAPE, "no index list: the groups name %lld stored rows, X holds %lld", (long long)n_total,
-               (long long)N);
     const int ctiles = (int)ceil_div(D, FG_TILE);
     const int64_t gemm_wgs = ceil_div(n_total, FG_TILE) * ctiles;
     AM_REQUIRE(gemm_wgs < ((int64_t)1 << 31), AM_ERR_BAD_SHAPE, "%lld rows x %d columns exceed the grid", (long long)n_total, D);
     Carver c(ws, ws_bytes);
     GroupsBuffers g;
     AM_REQUIRE(carve_groups(c, n_total, B, D, g), AM_ERR_WORKSPACE, "workspace too small: need %zu bytes, have %zu", c.off, ws_bytes);
-    AM_HIP_TRY(hipMemsetAsync(g.flag, 0, sizeof(unsigned long long), st));
-    AM_HIP_TRY(hipMemcpyAsync(g.offs, offsets, ((size_t)B + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(fg_centre_kernel<T>, dim3((unsigned)B), dim3(256), 0, st, X, N, ld, D, idx, (const int64_t*)g.offs, mu_y, cov_y, g.xc,
-                       g.stats, g.flag);
+    AM_TRY(upload_group_head(g.head, offsets, B, st));
+    const int64_t* offs = g.head.offs;
+    hipLaunchKernelGGL(fg_centre_kernel<T>, dim3((unsigned)B), dim3(256), 0, st, X, N, ld, D, idx, offs, mu_y, cov_y, g.xc,
+                       g.stats, g.head.flag);
     AM_LAUNCH_CHECK();
     hipLaunchKernelGGL(fg_gemm_kernel, dim3((unsigned)gemm_wgs), dim3(256), 0, st, (const double*)g.xc, n_total, D, cov_y, g.z, ctiles);
     AM_LAUNCH_CHECK();
     if (cls[0]) {
         hipLaunchKernelGGL(fg_solve_kernel<32>, dim3((unsigned)B), dim3(256), 0, st, (const double*)g.xc, (const double*)g.z,
-                           (const int64_t*)g.offs, D, (const double*)g.stats, out);
+                           offs, D, (const double*)g.stats, out);
         AM_LAUNCH_CHECK();
     }
     if (cls[1]) {
         hipLaunchKernelGGL(fg_solve_kernel<64>, dim3((unsigned)B), dim3(256), 0, st, (const double*)g.xc, (const double*)g.z,
-                           (const int64_t*)g.offs, D, (const double*)g.stats, out);
+                           offs, D, (const double*)g.stats, out);
         AM_LAUNCH_CHECK();
     }
     if (cls[2]) {
         hipLaunchKernelGGL(fg_solve_kernel<FG_MAX_ROWS>, dim3((unsigned)B), dim3(256), 0, st, (const double*)g.xc, (const double*)g.z,
-                           (const int64_t*)g.offs, D, (const double*)g.stats, out);
+                           offs, D, (const double*)g.stats, out);
         AM_LAUNCH_CHECK();
     }
     return AM_OK;

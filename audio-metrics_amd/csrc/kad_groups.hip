@@ -24,6 +24,7 @@
 //   kadg_finish_kernel  one workgroup per group: strided per-thread sums, then a tree -> out_groups[b] = {Sxx_b, Sxy_b}
 // The result depends on the list order and on nothing about where the rows are stored; two calls give the same bits.
 #include "am_common.h"
+#include "groups_common.h"
 #include "kad_common.h"
 #include "pairwise_common.h"
 #include <algorithm>
@@ -277,17 +278,14 @@ static GroupsPlan groups_plan(int64_t n_total, int64_t N2) {
 }
 
 struct GroupsWs {
-    unsigned long long* flag;    // first 8 bytes of the workspace
-    int64_t* offs;
+    GroupHead head;
     unsigned* rowoff;
     int* gid;
     double *xn, *yn, *rows, *pw, *pc;
 };
 
 static bool groups_carve(Carver& c, int64_t n_total, int B, int64_t N2, const GroupsPlan& p, GroupsWs& w) {
-    char* head = c.take<char>(8 + ((size_t)B + 1) * 8);
-    w.flag = reinterpret_cast<unsigned long long*>(head);
-    w.offs = reinterpret_cast<int64_t*>(head ? head + 8 : nullptr);
+    w.head = carve_group_head(c, B);
     w.rowoff = c.take<unsigned>((size_t)p.n_pad);
     w.gid = c.take<int>((size_t)p.n_pad);
     w.xn = c.take<double>((size_t)p.n_pad);
@@ -316,19 +314,15 @@ extern "C" int am_mmd_rbf_groups_f32(const float* X, int64_t N1, int64_t ldx, co
     AM_REQUIRE(X && offsets && Y && out_groups, AM_ERR_BAD_ARG, "null pointer (X, offsets, Y, out_groups)");
     AM_REQUIRE(N1 >= 1 && D >= 1 && B >= 1, AM_ERR_BAD_SHAPE, "X has shape %lld x %d, B=%d (all must be >= 1)", (long long)N1, D, B);
     AM_REQUIRE(N2 >= 2, AM_ERR_BAD_SHAPE, "N2=%lld: the unbiased MMD^2 needs two reference rows", (long long)N2);
-    AM_REQUIRE(aligned16(X) && aligned16(Y) && ldx % 4 == 0 && ldy % 4 == 0 && ldx >= D && ldy >= D, AM_ERR_BAD_ARG,
-               "X/Y must be 16-byte aligned with ld %% 4 == 0 and ld >= D (ldx=%lld, ldy=%lld, D=%d)", (long long)ldx, (long long)ldy, D);
-    AM_REQUIRE(!kad_too_large(N1, ldx) && !kad_too_large(N2, ldy), AM_ERR_BAD_SHAPE,
-               "N * ld * 4 bytes of a set >= 4 GiB: one buffer descriptor spans a matrix");
+    AM_TRY(check_group_rows(X, N1, ldx, D));
+    AM_REQUIRE(aligned16(Y) && ldy % 4 == 0 && ldy >= D, AM_ERR_BAD_ARG,
+               "Y must be 16-byte aligned with ld %% 4 == 0 and ld >= D (ldy=%lld, D=%d)", (long long)ldy, D);
+    AM_REQUIRE(!kad_too_large(N2, ldy), AM_ERR_BAD_SHAPE, "N2 * ldy * 4 bytes >= 4 GiB: one buffer descriptor spans the reference set");
     AM_REQUIRE(bw2_dev != nullptr || gamma >= 0.0, AM_ERR_BAD_ARG, "gamma must be >= 0 (or bw2_dev given)");
-    AM_REQUIRE(offsets[0] == 0, AM_ERR_BAD_ARG, "offsets[0]=%lld, must be 0", (long long)offsets[0]);
-    for (int b = 0; b < B; ++b)
-        AM_REQUIRE(offsets[b + 1] > offsets[b], AM_ERR_BAD_SHAPE, "offsets: group %d has %lld rows (offsets must increase strictly)", b,
-                   (long long)(offsets[b + 1] - offsets[b]));
-    const int64_t n_total = offsets[B];
+    int64_t n_total;
+    AM_TRY(check_group_offsets(offsets, B, 0, &n_total));
     AM_REQUIRE(n_total < ((int64_t)1 << 30), AM_ERR_BAD_SHAPE, "offsets name %lld list positions (must stay below 2^30)", (long long)n_total);
-    AM_REQUIRE(idx || n_total <= N1, AM_ERR_BAD_SHAPE, "no index list: the groups name %lld stored rows, X holds %lld", (long long)n_total,
-               (long long)N1);
+    AM_TRY(check_stored_rows(idx, n_total, N1));
     const GroupsPlan plan = groups_plan(n_total, N2);
     Carver c(ws, ws_bytes);
     GroupsWs w;
@@ -346,22 +340,22 @@ extern "C" int am_mmd_rbf_groups_f32(const float* X, int64_t N1, int64_t ldx, co
     const int chunk_w = (int)std::max<int64_t>(KAD_MAX_CHUNK, ceil_div(span, KADG_WITHIN_CHUNKS));
     const int nch_w = (int)ceil_div(span, chunk_w);      // <= min(TP, KADG_WITHIN_CHUNKS)
     hipStream_t st = static_cast<hipStream_t>(stream);
-    AM_HIP_TRY(hipMemsetAsync(w.flag, 0, sizeof(unsigned long long), st));
-    AM_HIP_TRY(hipMemcpyAsync(w.offs, offsets, ((size_t)B + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    AM_TRY(upload_group_head(w.head, offsets, B, st));
+    const int64_t* offs = w.head.offs;
     int rc = launch_kad_norms(Y, ldy, D, N2, w.yn, st);
     if (rc != AM_OK) return rc;
     hipLaunchKernelGGL(kadg_prep_kernel, dim3((unsigned)ceil_div(plan.n_pad, 4)), dim3(256), 0, st, X, N1, ldx, D, idx,
-                       (const int64_t*)w.offs, B, n_total, plan.n_pad, w.rowoff, w.xn, w.gid, w.flag);
+                       offs, B, n_total, plan.n_pad, w.rowoff, w.xn, w.gid, w.head.flag);
     AM_LAUNCH_CHECK();
     auto launch = [&](auto cross, auto within) -> int {
         AM_HIP_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(cross), (int)KADG_LDS_BYTES));
         AM_HIP_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(within), (int)KADG_LDS_BYTES));
         hipLaunchKernelGGL(cross, dim3((unsigned)plan.TP, (unsigned)plan.nch_c), dim3(ENGINE_THREADS), KADG_LDS_BYTES, st, X, N1, ldx,
-                           (const unsigned*)w.rowoff, (const double*)w.xn, (const int*)w.gid, (const int64_t*)w.offs, n_total, plan.n_pad,
+                           (const unsigned*)w.rowoff, (const double*)w.xn, (const int*)w.gid, offs, n_total, plan.n_pad,
                            Y, N2, ldy, (const double*)w.yn, D, plan.chunk_c, bw2_dev, gamma, w.pc);
         AM_LAUNCH_CHECK();
         hipLaunchKernelGGL(within, dim3((unsigned)plan.TP, (unsigned)nch_w), dim3(ENGINE_THREADS), KADG_LDS_BYTES, st, X, N1, ldx,
-                           (const unsigned*)w.rowoff, (const double*)w.xn, (const int*)w.gid, (const int64_t*)w.offs, n_total, plan.n_pad,
+                           (const unsigned*)w.rowoff, (const double*)w.xn, (const int*)w.gid, offs, n_total, plan.n_pad,
                            Y, N2, ldy, (const double*)w.yn, D, chunk_w, bw2_dev, gamma, w.pw);
         AM_LAUNCH_CHECK();
         return AM_OK;
@@ -373,7 +367,7 @@ extern "C" int am_mmd_rbf_groups_f32(const float* X, int64_t N1, int64_t ldx, co
     hipLaunchKernelGGL(kadg_rowsum_kernel, dim3((unsigned)ceil_div(n_total, 256)), dim3(256), 0, st, (const double*)w.pw, nch_w,
                        (const double*)w.pc, plan.nch_c, plan.n_pad, n_total, rows);
     AM_LAUNCH_CHECK();
-    hipLaunchKernelGGL(kadg_finish_kernel, dim3((unsigned)B), dim3(256), 0, st, (const double*)rows, (const int64_t*)w.offs, out_groups);
+    hipLaunchKernelGGL(kadg_finish_kernel, dim3((unsigned)B), dim3(256), 0, st, (const double*)rows, offs, out_groups);
     AM_LAUNCH_CHECK();
     return AM_OK;
 }

@@ -5,7 +5,7 @@
 // Arithmetic of one pair, exactly that of KnnEpilogue on the same 128 x 128 f32 tile engine (tile_engine.h,
 // v_mfma_f32_32x32x2_f32, dense_pipeline_early with the production schedule):
 //     d2 = max(fmaf(-2, <x, y>, |x|^2 + |y|^2), 0)       NaN -> +inf (clamp0); a padded column has |y|^2 = +inf
-// with the f32 row norms of row_sqnorm_kernel (pairwise.hip: launched from here, not copied).  Every reported squared
+// with the f32 row norms of row_sqnorm_kernel (launch_norms of pairwise.hip).  Every reported squared
 // distance therefore has the bits of the exact general kernel and of oracle/exact_c/pairwise_exact.c.
 //
 // Lists.  A list entry is ONE 64-bit key
@@ -23,8 +23,8 @@
 // Self exclusion is by INDEX (column i + self_offset is skipped for row i; duplicates of a row stay its neighbours), and
 // only the tiles the shifted diagonal crosses run the variant of the epilogue that tests for it.
 //
-// Column chunks: the (row block) x (column chunk) plan of the radii (work_item / choose_chunks of pairwise.hip, restated
-// below).  Partial lists: uint64 [nchunks][N][KCAP] in the caller's workspace; knn_search_merge_kernel takes the k smallest
+// Column chunks: the (row block) x (column chunk) plan of the radii (work_item / choose_chunks of pairwise_common.h).
+// Partial lists: uint64 [nchunks][N][KCAP] in the caller's workspace; knn_search_merge_kernel takes the k smallest
 // keys of a row and writes sqrt_rn(d2) (or d2) and the column as int64, -1 where the distance is +inf (fewer than k
 // finite candidates: M < k, M - 1 < k with exclusion, non-finite rows).
 //
@@ -37,11 +37,6 @@
 #include "pairwise_common.h"
 
 namespace am {
-
-// pairwise.hip: |x|^2 in f32 in the fixed order the exact kernels and oracle/exact_c share (defined there; this
-// translation unit only launches it)
-__global__ void row_sqnorm_kernel(const float* __restrict__ X, int64_t N, int64_t ld, int D, float* __restrict__ out);
-
 namespace search {
 
 constexpr int MAX_K = 32;
@@ -50,8 +45,6 @@ constexpr unsigned INF_BITS = 0x7f800000u;
 constexpr size_t LDS_BYTES = (ENGINE_LDS_FLOATS + 2 * TB) * sizeof(float);   // staging slabs + [2][128] column norms
 
 __host__ __device__ constexpr int kcap_for(int k) { return k <= 8 ? 8 : k <= 16 ? 16 : 32; }
-
-__device__ __forceinline__ float sqrt_rn(float x) { return (float)sqrt((double)x); }  // correctly rounded (as the radii)
 
 // Branch-free sorted insertion of a key into an ascending list of CAP keys (list_insert of tile_engine.h on uint64:
 // compare-exchange down the list, fully unrolled).  A key >= best[CAP-1] falls through.
@@ -64,21 +57,6 @@ __device__ __forceinline__ void key_insert(unsigned long long (&best)[CAP], unsi
         x = lt ? best[i] : x;
         best[i] = lo;
     }
-}
-
-// (row block, column chunk) of a workgroup: the plan of knn_partial_kernel (pairwise.hip: work_item) - consecutive blocks,
-// which land on different XCDs, take different chunks of the same row block
-struct WorkItem {
-    int64_t prow0, qtile0;
-    int ntiles, chunk;
-};
-__device__ __forceinline__ WorkItem work_item(int64_t q_tiles, int nchunks) {
-    WorkItem w;
-    w.chunk = blockIdx.x % nchunks;
-    w.prow0 = (int64_t)(blockIdx.x / nchunks) * TB;
-    w.qtile0 = q_tiles * w.chunk / nchunks;
-    w.ntiles = (int)(q_tiles * (w.chunk + 1) / nchunks - w.qtile0);
-    return w;
 }
 
 template <int KCAP>
@@ -176,6 +154,7 @@ knn_search_kernel(const float* __restrict__ X, int64_t N, int64_t ldx, const flo
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const LaneInfo L;
     const WorkItem w = work_item((M + TB - 1) / TB, nchunks);
+    const int chunk = blockIdx.x % nchunks;            // the chunk work_item gave this workgroup: its slice of `partial`
 
     KnnIndexEpilogue<KCAP> epi(L);
     epi.qnorm = ynorm;
@@ -209,7 +188,7 @@ knn_search_kernel(const float* __restrict__ X, int64_t N, int64_t ldx, const flo
 #pragma unroll
                 for (int s = 0; s < KCAP; ++s) m[s] = src[s];
                 for (int s = KCAP; s < 4 * KCAP; ++s) key_insert<KCAP>(m, src[s]);
-                unsigned long long* out = partial + ((int64_t)w.chunk * N + i) * KCAP;
+                unsigned long long* out = partial + ((int64_t)chunk * N + i) * KCAP;
 #pragma unroll
                 for (int s = 0; s < KCAP; ++s) out[s] = m[s];
             }
@@ -242,30 +221,9 @@ __global__ void __launch_bounds__(256) knn_search_merge_kernel(const unsigned lo
     }
 }
 
-// column chunks per row block (pairwise.hip: choose_chunks): >= 8192 workgroups where the column tiles allow it, one chunk
-// per XCD at least, 64 at most
-static int choose_chunks(int64_t p_rows, int64_t q_rows) {
-    const int64_t row_blocks = ceil_div(p_rows, TB);
-    const int64_t q_tiles = ceil_div(q_rows, TB);
-    int64_t want = ceil_div(8192, row_blocks);
-    if (want < 8) want = 8;
-    want = ceil_div(want, 8) * 8;
-    if (want > q_tiles) want = q_tiles;
-    if (want > 64) want = 64;
-    return (int)(want < 1 ? 1 : want);
-}
-
 static bool shape_ok(int64_t N, int64_t M, int D, int k) {
     // columns are the low 32 bits of a key (0xffffffff = none); one grid dimension holds row blocks x chunks
     return N >= 1 && M >= 1 && D >= 1 && k >= 1 && k <= MAX_K && M < (int64_t)0xffffffffll && ceil_div(N, TB) * 64 < (int64_t)0x7fffffff;
-}
-
-static int check_matrix(const float* p, int64_t n, int64_t ld, int D, const char* name) {
-    AM_REQUIRE(p != nullptr, AM_ERR_BAD_ARG, "%s is null", name);
-    AM_REQUIRE(n >= 1 && D >= 1, AM_ERR_BAD_SHAPE, "%s has shape %lld x %d", name, (long long)n, D);
-    AM_REQUIRE(aligned16(p) && ld % 4 == 0 && ld >= D, AM_ERR_BAD_ARG,
-               "%s must be 16-byte aligned with ld %% 4 == 0 and ld >= D (ld=%lld, D=%d)", name, (long long)ld, D);
-    return AM_OK;
 }
 
 struct Buffers {
@@ -307,25 +265,25 @@ extern "C" size_t am_knn_search_workspace_bytes(int64_t N, int64_t M, int D, int
     if (!search::shape_ok(N, M, D, k)) return 0;
     Carver c(nullptr, 0);
     search::Buffers b;
-    search::carve(c, N, M, k, search::choose_chunks(N, M), b);
+    search::carve(c, N, M, k, choose_chunks(N, M), b);
     return c.off;
 }
 
 extern "C" int am_knn_search_chunks(int64_t N, int64_t M, int D, int k) {
-    return search::shape_ok(N, M, D, k) ? search::choose_chunks(N, M) : 0;
+    return search::shape_ok(N, M, D, k) ? choose_chunks(N, M) : 0;
 }
 
 extern "C" int am_knn_search_f32(const float* X, int64_t N, int64_t ldx, const float* Y, int64_t M, int64_t ldy, int D, int k,
                                  int64_t self_offset, int squared, float* out_dist, int64_t* out_idx, void* ws, size_t ws_bytes,
                                  am_stream_t stream) {
     int rc;
-    if ((rc = search::check_matrix(X, N, ldx, D, "X")) != AM_OK) return rc;
-    if ((rc = search::check_matrix(Y, M, ldy, D, "Y")) != AM_OK) return rc;
+    if ((rc = check_matrix(X, N, ldx, D, "X")) != AM_OK) return rc;
+    if ((rc = check_matrix(Y, M, ldy, D, "Y")) != AM_OK) return rc;
     AM_REQUIRE(out_dist != nullptr && out_idx != nullptr, AM_ERR_BAD_ARG, "%s is null", out_dist == nullptr ? "out_dist" : "out_idx");
     AM_REQUIRE(k >= 1 && k <= search::MAX_K, AM_ERR_BAD_SHAPE, "k = %d: the search keeps 1 .. %d neighbours per row", k, search::MAX_K);
     AM_REQUIRE(search::shape_ok(N, M, D, k), AM_ERR_BAD_SHAPE, "N=%lld M=%lld: a column index takes 32 bits of a list key (M < 2^32 - 1)",
                (long long)N, (long long)M);
-    const int nchunks = search::choose_chunks(N, M);
+    const int nchunks = choose_chunks(N, M);
     Carver c(ws, ws_bytes);
     search::Buffers b;
     search::carve(c, N, M, k, nchunks, b);
@@ -334,12 +292,8 @@ extern "C" int am_knn_search_f32(const float* X, int64_t N, int64_t ldx, const f
     // a column past the end excludes nothing; the kernel adds row indices to the offset
     if (self_offset >= M) self_offset = -1;
     const bool self = (Y == X && M == N && ldy == ldx);
-    hipLaunchKernelGGL(row_sqnorm_kernel, dim3((unsigned)ceil_div(N, 4)), dim3(256), 0, st, X, N, ldx, D, b.xn);
-    AM_LAUNCH_CHECK();
-    if (!self) {
-        hipLaunchKernelGGL(row_sqnorm_kernel, dim3((unsigned)ceil_div(M, 4)), dim3(256), 0, st, Y, M, ldy, D, b.yn);
-        AM_LAUNCH_CHECK();
-    }
+    if ((rc = launch_norms(X, N, ldx, D, b.xn, st)) != AM_OK) return rc;
+    if (!self && (rc = launch_norms(Y, M, ldy, D, b.yn, st)) != AM_OK) return rc;
     const float* yn = self ? b.xn : b.yn;
     switch (search::kcap_for(k)) {
         case 8:  return search::run<8>(X, N, ldx, b.xn, Y, M, ldy, yn, D, k, nchunks, self_offset, squared, b.partial, out_dist, out_idx, st);

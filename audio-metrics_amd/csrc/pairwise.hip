@@ -39,8 +39,6 @@ __global__ void __launch_bounds__(256) row_sqnorm_kernel(const float* __restrict
 }
 
 // ------------------------------------------------- radius -> squared threshold
-__device__ __forceinline__ float sqrt_rn(float x) { return (float)sqrt((double)x); }  // correctly rounded
-
 __device__ __forceinline__ float threshold_of_radius(float R) {
     if (!(R > 0.f)) return 0.f;                     // R == 0 (or NaN): nothing is strictly inside
     if (isinf(R)) return R;
@@ -69,27 +67,6 @@ struct DenseRows {            // rows base + (tile0 + t) * 128 + local row, zero
         return g < n ? base + g * ld : nullptr;
     }
 };
-
-struct WorkItem {
-    int64_t prow0;     // first P row of this workgroup
-    int64_t qtile0;    // first Q tile of this workgroup's column chunk
-    int ntiles;
-};
-
-__device__ __forceinline__ WorkItem work_item(int64_t q_tiles, int nchunks, int order = 0) {
-    int chunk = blockIdx.x % nchunks;              // consecutive blocks (= different XCDs) take different chunks
-    int64_t rb = blockIdx.x / nchunks;
-    if (order == 1) {                              // experiment: chunk-major (all row blocks of chunk 0 first)
-        const int64_t nrb = gridDim.x / nchunks;
-        chunk = (int)(blockIdx.x / nrb);
-        rb = blockIdx.x % nrb;
-    }
-    WorkItem w;
-    w.prow0 = rb * TB;
-    w.qtile0 = q_tiles * chunk / nchunks;
-    w.ntiles = (int)(q_tiles * (chunk + 1) / nchunks - w.qtile0);
-    return w;
-}
 
 // XCD-grouped form of the same (row block, column chunk) grid for the f16 filter kernels, whose operand traffic is
 // 16x the exact kernels' per unit of time and therefore has to come from L2: block b runs on XCD b % 8
@@ -838,31 +815,11 @@ __global__ void __launch_bounds__(256) prdc_reduce_kernel(const int32_t* __restr
 }
 
 // ------------------------------------------------------------------ host side
-static int choose_chunks(int64_t p_rows, int64_t q_rows) {
-    const int64_t row_blocks = ceil_div(p_rows, TB);
-    const int64_t q_tiles = ceil_div(q_rows, TB);
-    static const int target = env_int("AM_WG_TARGET", 8192);
-    int64_t want = ceil_div(target, row_blocks);         // aim for >= 8192 workgroups: 16 rounds of 256 CUs x 2 keeps the tail ~2%
-    if (want < 8) want = 8;                              // one chunk per XCD at least
-    want = ceil_div(want, 8) * 8;
-    if (want > q_tiles) want = q_tiles;
-    if (want > 64) want = 64;
-    return (int)(want < 1 ? 1 : want);
-}
-
 static int kcap_for(int k1) { return k1 <= 6 ? 6 : k1 <= 11 ? 11 : k1 <= 16 ? 16 : 32; }
 
 constexpr size_t PAIRWISE_LDS_BYTES = (ENGINE_LDS_FLOATS + 4 * TB) * sizeof(float);
 
-static int check_matrix(const float* p, int64_t n, int64_t ld, int D, const char* name) {
-    AM_REQUIRE(p != nullptr, AM_ERR_BAD_ARG, "%s is null", name);
-    AM_REQUIRE(n >= 1 && D >= 1, AM_ERR_BAD_SHAPE, "%s has shape %lld x %d", name, (long long)n, D);
-    AM_REQUIRE(aligned16(p) && ld % 4 == 0 && ld >= D, AM_ERR_BAD_ARG,
-               "%s must be 16-byte aligned with ld %% 4 == 0 and ld >= D (ld=%lld, D=%d)", name, (long long)ld, D);
-    return AM_OK;
-}
-
-static int launch_norms(const float* X, int64_t N, int64_t ld, int D, float* out, hipStream_t st) {
+int launch_norms(const float* X, int64_t N, int64_t ld, int D, float* out, hipStream_t st) {
     hipLaunchKernelGGL(row_sqnorm_kernel, dim3((unsigned)ceil_div(N, 4)), dim3(256), 0, st, X, N, ld, D, out);
     AM_LAUNCH_CHECK();
     return AM_OK;

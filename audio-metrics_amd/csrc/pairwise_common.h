@@ -1,6 +1,6 @@
-// Helpers shared by the two translation units of the PRDC path: pairwise.hip (exact f32 kernels, the 128-row f16 filter
-// kernels and every host entry point) and pairwise_wide.hip (the 256 x 256 f16 filter kernels of wide_engine.h, built
-// separately so that the two compile in parallel).
+// Helpers shared by the translation units of the PRDC path: pairwise.hip (exact f32 kernels, the 128-row f16 filter
+// kernels and every host entry point), pairwise_wide.hip (the 256 x 256 f16 filter kernels of wide_engine.h, built
+// separately so that the two compile in parallel) and knn_search.hip (the search on the plan and the norms of the radii).
 #pragma once
 #include "am_common.h"
 #include "tile_engine.h"
@@ -27,6 +27,55 @@ static int engine_variant() {
 static constexpr int env_int(const char*, int dflt) { return dflt; }
 static constexpr int engine_variant() { return EV_DEFAULT; }
 #endif
+
+// ---- the (row block) x (column chunk) plan of the exact tile kernels: the radii, the counts and the search (knn_search.hip)
+struct WorkItem {
+    int64_t prow0;     // first P row of this workgroup
+    int64_t qtile0;    // first Q tile of this workgroup's column chunk
+    int ntiles;
+};
+
+__device__ __forceinline__ WorkItem work_item(int64_t q_tiles, int nchunks, int order = 0) {
+    int chunk = blockIdx.x % nchunks;              // consecutive blocks (= different XCDs) take different chunks
+    int64_t rb = blockIdx.x / nchunks;
+    if (order == 1) {                              // experiment: chunk-major (all row blocks of chunk 0 first)
+        const int64_t nrb = gridDim.x / nchunks;
+        chunk = (int)(blockIdx.x / nrb);
+        rb = blockIdx.x % nrb;
+    }
+    WorkItem w;
+    w.prow0 = rb * TB;
+    w.qtile0 = q_tiles * chunk / nchunks;
+    w.ntiles = (int)(q_tiles * (chunk + 1) / nchunks - w.qtile0);
+    return w;
+}
+
+// column chunks per row block
+static inline int choose_chunks(int64_t p_rows, int64_t q_rows) {
+    const int64_t row_blocks = ceil_div(p_rows, TB);
+    const int64_t q_tiles = ceil_div(q_rows, TB);
+    static const int target = env_int("AM_WG_TARGET", 8192);
+    int64_t want = ceil_div(target, row_blocks);         // aim for >= 8192 workgroups: 16 rounds of 256 CUs x 2 keeps the tail ~2%
+    if (want < 8) want = 8;                              // one chunk per XCD at least
+    want = ceil_div(want, 8) * 8;
+    if (want > q_tiles) want = q_tiles;
+    if (want > 64) want = 64;
+    return (int)(want < 1 ? 1 : want);
+}
+
+static inline int check_matrix(const float* p, int64_t n, int64_t ld, int D, const char* name) {
+    AM_REQUIRE(p != nullptr, AM_ERR_BAD_ARG, "%s is null", name);
+    AM_REQUIRE(n >= 1 && D >= 1, AM_ERR_BAD_SHAPE, "%s has shape %lld x %d", name, (long long)n, D);
+    AM_REQUIRE(aligned16(p) && ld % 4 == 0 && ld >= D, AM_ERR_BAD_ARG,
+               "%s must be 16-byte aligned with ld %% 4 == 0 and ld >= D (ld=%lld, D=%d)", name, (long long)ld, D);
+    return AM_OK;
+}
+
+__device__ __forceinline__ float sqrt_rn(float x) { return (float)sqrt((double)x); }  // correctly rounded
+
+// |x|^2 in f32 in the fixed order the exact kernels and oracle/exact_c share (pairwise.hip)
+__global__ void row_sqnorm_kernel(const float* __restrict__ X, int64_t N, int64_t ld, int D, float* __restrict__ out);
+int launch_norms(const float* X, int64_t N, int64_t ld, int D, float* out, hipStream_t st);
 
 
 // Scaled f16 copies of the filter passes (pairwise_fast.h): a matrix whose largest |element| has the f32 bit pattern

@@ -13,6 +13,7 @@
 //   pass 4  covs[b] = (sum of the subset's partial tiles, in chunk order) / (n_b - 1), mirrored; n_b == 1 -> 0
 // All sums run in a fixed order: the result is deterministic for a given index list.
 #include "am_common.h"
+#include "groups_common.h"
 #include "tile_engine.h"
 #include <algorithm>
 #include <vector>
@@ -359,14 +360,12 @@ static GatherPlan plan_gather(int64_t n_total, int B, int D, bool f64) {
 }
 
 struct GatherBuffers {
-    unsigned long long* flag;
-    int64_t* offs;
+    GroupHead head;
     double *cs_part, *sc_part;
 };
 
 static bool carve_gather(Carver& c, int B, int D, const GatherPlan& p, GatherBuffers& g) {
-    g.flag = c.take<unsigned long long>(1);
-    g.offs = c.take<int64_t>((size_t)B + 1);
+    g.head = carve_group_head(c, B);
     g.cs_part = c.take<double>((size_t)p.max_chunks * D);
     g.sc_part = c.take<double>((size_t)p.max_chunks * p.ntri * p.tile * p.tile);
     return c.ok();
@@ -379,20 +378,9 @@ static int stats_gather(const T* X, int64_t N, int64_t ld, int D, const int64_t*
     AM_REQUIRE(X && idx && offsets && means && covs, AM_ERR_BAD_ARG, "null pointer");
     AM_REQUIRE(N >= 1 && D >= 1 && B >= 1 && B <= 65535, AM_ERR_BAD_SHAPE, "X has shape %lld x %d, B=%d (1 <= B <= 65535)",
                (long long)N, D, B);
-    if (F64) {
-        AM_REQUIRE(D <= 8192 && ld >= D, AM_ERR_BAD_ARG, "float64 rows: D=%d (<= 8192), ld=%lld (>= D)", D, (long long)ld);
-    } else {
-        AM_REQUIRE(aligned16(X) && ld % 4 == 0 && ld >= D, AM_ERR_BAD_ARG,
-                   "X must be 16-byte aligned with ld %% 4 == 0 and ld >= D (ld=%lld, D=%d)", (long long)ld, D);
-        AM_REQUIRE(N * ld < ((int64_t)1 << 30), AM_ERR_BAD_SHAPE,
-                   "gathered float32 statistics address the stored matrix with 32-bit element offsets: %lld x %lld floats is 4 GiB or more",
-                   (long long)N, (long long)ld);
-    }
-    AM_REQUIRE(offsets[0] == 0, AM_ERR_BAD_ARG, "offsets[0]=%lld, must be 0", (long long)offsets[0]);
-    for (int b = 0; b < B; ++b)
-        AM_REQUIRE(offsets[b + 1] > offsets[b], AM_ERR_BAD_SHAPE, "subset %d is empty (offsets %lld, %lld)", b, (long long)offsets[b],
-                   (long long)offsets[b + 1]);
-    const int64_t n_total = offsets[B];
+    AM_TRY(check_group_rows(X, N, ld, D));
+    int64_t n_total;
+    AM_TRY(check_group_offsets(offsets, B, 0, &n_total));
     const GatherPlan p = plan_gather(n_total, B, D, F64);
     int64_t chunks = 0;
     for (int b = 0; b < B; ++b) chunks += ceil_div(offsets[b + 1] - offsets[b], p.R);
@@ -401,26 +389,26 @@ static int stats_gather(const T* X, int64_t N, int64_t ld, int D, const int64_t*
     Carver c(ws, ws_bytes);
     GatherBuffers g;
     AM_REQUIRE(carve_gather(c, B, D, p, g), AM_ERR_WORKSPACE, "workspace too small: need %zu bytes, have %zu", c.off, ws_bytes);
-    AM_HIP_TRY(hipMemsetAsync(g.flag, 0, sizeof(unsigned long long), st));
-    AM_HIP_TRY(hipMemcpyAsync(g.offs, offsets, ((size_t)B + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    AM_TRY(upload_group_head(g.head, offsets, B, st));
+    const int64_t* offs = g.head.offs;
     hipLaunchKernelGGL((sg_colsum_kernel<T, F64 ? 1 : 4>), dim3((unsigned)chunks), dim3(256), 0, st, X, N, ld, D, idx,
-                       (const int64_t*)g.offs, B, p.R, g.cs_part, g.flag);
+                       offs, B, p.R, g.cs_part, g.head.flag);
     AM_LAUNCH_CHECK();
     hipLaunchKernelGGL(sg_mean_kernel, dim3((unsigned)ceil_div(D, 256), (unsigned)B), dim3(256), 0, st, (const double*)g.cs_part,
-                       (const int64_t*)g.offs, p.R, D, means);
+                       offs, p.R, D, means);
     AM_LAUNCH_CHECK();
     if constexpr (F64) {
         hipLaunchKernelGGL(sg_scatter64_kernel, dim3((unsigned)(chunks * p.ntri)), dim3(256), 0, st, X, N, ld, D, idx,
-                           (const int64_t*)g.offs, B, p.R, (const double*)means, p.ntri, g.sc_part);
+                           offs, B, p.R, (const double*)means, p.ntri, g.sc_part);
         AM_LAUNCH_CHECK();
         hipLaunchKernelGGL(sg_reduce_kernel<SG64_TILE>, dim3(SG64_TILE * SG64_TILE / 256, (unsigned)p.ntri, (unsigned)B), dim3(256), 0,
-                           st, (const double*)g.sc_part, (const int64_t*)g.offs, p.R, p.ntri, D, covs);
+                           st, (const double*)g.sc_part, offs, p.R, p.ntri, D, covs);
     } else {
         hipLaunchKernelGGL(sg_scatter_kernel, dim3((unsigned)(chunks * p.ntri)), dim3(ENGINE_THREADS), 0, st, X, N, ld, D, idx,
-                           (const int64_t*)g.offs, B, p.R, (const double*)means, p.ntri, g.sc_part);
+                           offs, B, p.R, (const double*)means, p.ntri, g.sc_part);
         AM_LAUNCH_CHECK();
         hipLaunchKernelGGL(sg_reduce_kernel<TB>, dim3(TB * TB / 256, (unsigned)p.ntri, (unsigned)B), dim3(256), 0, st,
-                           (const double*)g.sc_part, (const int64_t*)g.offs, p.R, p.ntri, D, covs);
+                           (const double*)g.sc_part, offs, p.R, p.ntri, D, covs);
     }
     AM_LAUNCH_CHECK();
     return AM_OK;

@@ -223,6 +223,63 @@ def _f64(t, name):
     return t
 
 
+# ------------------------------------------------------------------ row groups: rows[idx[offsets[b]:offsets[b + 1]]]
+def _group_offsets(offsets):
+    """(the offsets as a list of ints, B, the same as a ctypes int64 array for the C ABI)."""
+    offs = [int(o) for o in offsets]
+    b = len(offs) - 1
+    if b < 1 or offs[0] != 0 or any(offs[i + 1] <= offs[i] for i in range(b)):
+        raise ValueError(f"offsets must start at 0 and increase strictly (got {offs[:4]}{'...' if b > 3 else ''})")
+    return offs, b, (ctypes.c_int64 * (b + 1))(*offs)
+
+
+def _group_index(idx, listed, like):
+    """The index list as a contiguous int64 tensor on the device of `like` with at least `listed` entries; None (the rows
+    in stored order, where the entry point allows it) passes through."""
+    if idx is None:
+        return None
+    _require_cuda(idx, "idx")
+    idx = idx.to(torch.int64).contiguous()
+    _same_device(like, idx)
+    if idx.numel() < listed:
+        raise ValueError(f"idx holds {idx.numel()} entries, offsets name {listed}")
+    return idx
+
+
+def _index_check(ws, idx, n, noun):
+    """check() of a group-list call: the one host read of the flag word at the head of its workspace - 1 + the position
+    of an index outside [0, n), or 0.  Without an index list the offending value is the position itself."""
+    def check():
+        flag = int(ws[:8].view(torch.int64).item())
+        if flag != 0:
+            pos = flag - 1
+            bad = int(idx[pos].item()) if idx is not None else pos
+            raise ValueError(f"idx[{pos}] = {bad} is outside [0, {n}) ({noun} are named by stored-row index)")
+    return check
+
+
+def _records_out(out, b, dev, whose):
+    """The f64 [B, 5] record tensor of the batched Frechet entry points: a fresh one, or the caller's once checked."""
+    if out is None:
+        return torch.empty((b, 5), dtype=torch.float64, device=dev)
+    if out.dtype != torch.float64 or tuple(out.shape) != (b, 5) or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"out must be a contiguous float64 [B, 5] tensor on the {whose} device")
+    return out
+
+
+def _bandwidth_args(bw2, gamma):
+    """The (bw2 pointer, gamma) arguments of the Gaussian-kernel entry points from exactly one of a float32 device scalar
+    and a number."""
+    if (bw2 is None) == (gamma is None):
+        raise ValueError("exactly one of bw2 (device scalar) and gamma (number) must be given")
+    if bw2 is None:
+        return ctypes.c_void_p(None), float(gamma)
+    _require_cuda(bw2, "bw2")
+    if bw2.dtype != torch.float32 or bw2.numel() != 1:
+        raise ValueError("bw2 must be a float32 device scalar")
+    return _ptr(bw2), 0.0
+
+
 # ------------------------------------------------------------------ statistics
 def stats(e):
     """mean f64[D], unbiased covariance f64[D, D] of the rows of e (data.py:37-58), computed in the dtype of e."""
@@ -269,29 +326,16 @@ def stats_gather(x, idx, offsets, defer_check=False):
     x = as_matrix64(x) if f64 else as_matrix(x)
     _require_cuda(idx, "idx")
     n, d = x.shape
-    offs = [int(o) for o in offsets]
-    b = len(offs) - 1
-    if b < 1 or offs[0] != 0 or any(offs[i + 1] <= offs[i] for i in range(b)):
-        raise ValueError(f"offsets must start at 0 and increase strictly (got {offs[:4]}{'...' if b > 3 else ''})")
-    idx = idx.to(torch.int64).contiguous()
-    _same_device(x, idx)
-    if idx.numel() < offs[-1]:
-        raise ValueError(f"idx holds {idx.numel()} entries, offsets name {offs[-1]}")
+    offs, b, host_offs = _group_offsets(offsets)
+    idx = _group_index(idx, offs[-1], x)
     dev = x.device
     means = torch.empty((b, d), dtype=torch.float64, device=dev)
     covs = torch.empty((b, d, d), dtype=torch.float64, device=dev)
     nb = lib.am_stats_gather_workspace_bytes(offs[-1], b, d)
     ws = _workspace(nb, dev)
-    host_offs = (ctypes.c_int64 * (b + 1))(*offs)
     _call(lib, "am_stats_gather_f64" if f64 else "am_stats_gather_f32", dev, _ptr(x), n, _ld64(x) if f64 else _ld(x), d, _ptr(idx),
           ctypes.cast(host_offs, ctypes.c_void_p), b, _ptr(means), _ptr(covs), _ptr(ws), nb)
-
-    def check():
-        flag = int(ws[:8].view(torch.int64).item())          # the one host read: 1 + position of an out-of-range index, or 0
-        if flag != 0:
-            pos = flag - 1
-            raise ValueError(f"idx[{pos}] = {int(idx[pos].item())} is outside [0, {n}) (subset rows are named by stored-row index)")
-
+    check = _index_check(ws, idx, n, "subset rows")
     if defer_check:
         return means, covs, check
     check()
@@ -451,10 +495,7 @@ def frechet_batch(mu_x, cov_x, mu_y, cov_y, max_iter=64, tol=1e-13, out=None):
         raise ValueError(f"inconsistent shapes: mu {tuple(mu_x.shape)}/{tuple(mu_y.shape)}, "
                          f"cov {tuple(cov_x.shape)}/{tuple(cov_y.shape)}")
     dev = _same_device(mu_x, cov_x, mu_y, cov_y)
-    if out is None:
-        out = torch.empty((b, 5), dtype=torch.float64, device=dev)
-    elif out.dtype != torch.float64 or tuple(out.shape) != (b, 5) or not out.is_contiguous() or out.device != dev:
-        raise ValueError("out must be a contiguous float64 [B, 5] tensor on the statistics' device")
+    out = _records_out(out, b, dev, "statistics'")
     per_set = max(int(lib.am_frechet_batch_workspace_bytes(1, d)), 1)
     chunk = max(1, min(b, FRECHET_BATCH_WS_CAP // per_set))
     failure = None
@@ -502,36 +543,16 @@ def frechet_groups(rows, idx, offsets, mu_y, cov_y, out=None):
     mu_y, cov_y = _f64(mu_y, "mu_y"), _f64(cov_y, "cov_y")
     if mu_y.numel() != d or tuple(cov_y.shape) != (d, d):
         raise ValueError(f"inconsistent shapes: rows {tuple(rows.shape)}, mu_y {tuple(mu_y.shape)}, cov_y {tuple(cov_y.shape)}")
-    offs = [int(o) for o in offsets]
-    b = len(offs) - 1
-    if b < 1 or offs[0] != 0 or any(offs[i + 1] <= offs[i] for i in range(b)):
-        raise ValueError(f"offsets must start at 0 and increase strictly (got {offs[:4]}{'...' if b > 3 else ''})")
+    offs, b, host_offs = _group_offsets(offsets)
     dev = _same_device(rows, mu_y, cov_y)
-    if idx is not None:
-        _require_cuda(idx, "idx")
-        idx = idx.to(torch.int64).contiguous()
-        _same_device(rows, idx)
-        if idx.numel() < offs[-1]:
-            raise ValueError(f"idx holds {idx.numel()} entries, offsets name {offs[-1]}")
-    if out is None:
-        out = torch.empty((b, 5), dtype=torch.float64, device=dev)
-    elif out.dtype != torch.float64 or tuple(out.shape) != (b, 5) or not out.is_contiguous() or out.device != dev:
-        raise ValueError("out must be a contiguous float64 [B, 5] tensor on the rows' device")
+    idx = _group_index(idx, offs[-1], rows)
+    out = _records_out(out, b, dev, "rows'")
     nb = lib.am_frechet_groups_workspace_bytes(offs[-1], b, d)
     ws = _workspace(nb, dev)
-    host_offs = (ctypes.c_int64 * (b + 1))(*offs)
     _call(lib, "am_frechet_groups_f64" if f64 else "am_frechet_groups_f32", dev, _ptr(rows), n, _ld64(rows) if f64 else _ld(rows), d,
           _ptr(idx) if idx is not None else ctypes.c_void_p(None), ctypes.cast(host_offs, ctypes.c_void_p), b, _ptr(mu_y), _ptr(cov_y),
           _ptr(out), _ptr(ws), nb)
-
-    def check():
-        flag = int(ws[:8].view(torch.int64).item())          # the one host read: 1 + position of an out-of-range index, or 0
-        if flag != 0:
-            pos = flag - 1
-            bad = int(idx[pos].item()) if idx is not None else pos
-            raise ValueError(f"idx[{pos}] = {bad} is outside [0, {n}) (group rows are named by stored-row index)")
-
-    return out, check
+    return out, _index_check(ws, idx, n, "group rows")
 
 
 class FrechetJob:
@@ -672,8 +693,7 @@ def mmd_rbf_sums(x, y, bw2=None, gamma=None, blocks=7, out=None):
     lib = _lib.load()
     if is_f64(x) or is_f64(y):
         raise NotImplementedError("mmd_rbf_sums takes float32 rows (the float64 matrix-core form is not implemented)")
-    if (bw2 is None) == (gamma is None):
-        raise ValueError("exactly one of bw2 (device scalar) and gamma (number) must be given")
+    bw2_arg, gamma_arg = _bandwidth_args(bw2, gamma)
     x, y = as_matrix(x, "x"), as_matrix(y, "y")
     dev = _same_device(x, y)
     if x.shape[1] != y.shape[1]:
@@ -682,16 +702,11 @@ def mmd_rbf_sums(x, y, bw2=None, gamma=None, blocks=7, out=None):
         out = torch.full((3,), float("nan"), dtype=torch.float64, device=dev)
     elif not (out.is_cuda and out.dtype == torch.float64 and out.numel() == 3 and out.is_contiguous()):
         raise ValueError("out must be a contiguous float64[3] device tensor")
-    if bw2 is not None:
-        _require_cuda(bw2, "bw2")
-        if bw2.dtype != torch.float32 or bw2.numel() != 1:
-            raise ValueError("bw2 must be a float32 device scalar")
     blocks = int(blocks)
     nb = lib.am_mmd_rbf_workspace_bytes(x.shape[0], y.shape[0], x.shape[1], blocks)
     ws = _workspace(nb, dev)
     _call(lib, "am_mmd_rbf_f32", dev, _ptr(x), x.shape[0], _ld(x), _ptr(y), y.shape[0], _ld(y), x.shape[1],
-          _ptr(bw2) if bw2 is not None else ctypes.c_void_p(None), 0.0 if gamma is None else float(gamma), blocks, _ptr(out),
-          _ptr(ws), nb)
+          bw2_arg, gamma_arg, blocks, _ptr(out), _ptr(ws), nb)
     return out
 
 
@@ -707,44 +722,23 @@ def mmd_rbf_group_sums(x, idx, offsets, y, bw2=None, gamma=None, rows=False):
     lib = _lib.load()
     if is_f64(x) or is_f64(y):
         raise NotImplementedError("mmd_rbf_group_sums takes float32 rows (the float64 matrix-core form is not implemented)")
-    if (bw2 is None) == (gamma is None):
-        raise ValueError("exactly one of bw2 (device scalar) and gamma (number) must be given")
+    bw2_arg, gamma_arg = _bandwidth_args(bw2, gamma)
     x, y = as_matrix(x, "x"), as_matrix(y, "y")
     dev = _same_device(x, y)
     n, d = x.shape
     if d != y.shape[1]:
         raise ValueError(f"feature widths differ: {d} and {y.shape[1]}")
-    offs = [int(o) for o in offsets]
-    b = len(offs) - 1
-    if b < 1 or offs[0] != 0 or any(offs[i + 1] <= offs[i] for i in range(b)):
-        raise ValueError(f"offsets must start at 0 and increase strictly (got {offs[:4]}{'...' if b > 3 else ''})")
-    if idx is not None:
-        _require_cuda(idx, "idx")
-        idx = idx.to(torch.int64).contiguous()
-        _same_device(x, idx)
-        if idx.numel() < offs[-1]:
-            raise ValueError(f"idx holds {idx.numel()} entries, offsets name {offs[-1]}")
-    if bw2 is not None:
-        _require_cuda(bw2, "bw2")
-        if bw2.dtype != torch.float32 or bw2.numel() != 1:
-            raise ValueError("bw2 must be a float32 device scalar")
+    offs, b, host_offs = _group_offsets(offsets)
+    idx = _group_index(idx, offs[-1], x)
     out_groups = torch.empty((b, 2), dtype=torch.float64, device=dev)
     out_rows = torch.empty((offs[-1], 2), dtype=torch.float64, device=dev) if rows else None
     nb = lib.am_mmd_rbf_groups_workspace_bytes(offs[-1], b, y.shape[0], d)
     ws = _workspace(nb, dev)
-    host_offs = (ctypes.c_int64 * (b + 1))(*offs)
     null = ctypes.c_void_p(None)
     _call(lib, "am_mmd_rbf_groups_f32", dev, _ptr(x), n, _ld(x), _ptr(idx) if idx is not None else null,
-          ctypes.cast(host_offs, ctypes.c_void_p), b, _ptr(y), y.shape[0], _ld(y), d, _ptr(bw2) if bw2 is not None else null,
-          0.0 if gamma is None else float(gamma), _ptr(out_groups), _ptr(out_rows) if rows else null, _ptr(ws), nb)
-
-    def check():
-        flag = int(ws[:8].view(torch.int64).item())          # the one host read: 1 + position of an out-of-range index, or 0
-        if flag != 0:
-            pos = flag - 1
-            bad = int(idx[pos].item()) if idx is not None else pos
-            raise ValueError(f"idx[{pos}] = {bad} is outside [0, {n}) (group rows are named by stored-row index)")
-
+          ctypes.cast(host_offs, ctypes.c_void_p), b, _ptr(y), y.shape[0], _ld(y), d, bw2_arg, gamma_arg, _ptr(out_groups),
+          _ptr(out_rows) if rows else null, _ptr(ws), nb)
+    check = _index_check(ws, idx, n, "group rows")
     return (out_groups, out_rows, check) if rows else (out_groups, check)
 
 

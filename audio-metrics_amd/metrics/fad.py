@@ -4,6 +4,7 @@ import torch
 
 from .. import hip_ops as ops
 from ..data import AudioMetricsData, ensure_tensor
+from ._groups import labelled_rows, sort_into_groups
 
 NS_MAX_ITER = 64
 NS_TOL = 1e-13
@@ -129,24 +130,6 @@ def frechet_distance_inf(x: AudioMetricsData, y: AudioMetricsData, steps=FAD_INF
 
 
 # ------------------------------------------------------------------ per-group ("per-song") Frechet distance
-def _group_labels(groups):
-    """The labels as a 1-D integer torch tensor (host or device, as given); no device call."""
-    if isinstance(groups, torch.Tensor):
-        labels = groups
-        if labels.dtype == torch.bool or labels.is_floating_point() or labels.is_complex():
-            raise ValueError(f"groups must hold integer labels, got dtype {labels.dtype}")
-    else:
-        arr = np.asarray(groups)
-        if arr.size and arr.dtype.kind not in "iu":
-            raise ValueError(f"groups must hold integer labels, got dtype {arr.dtype}")
-        if arr.dtype.kind == "u" and arr.size and int(arr.max()) > np.iinfo(np.int64).max:
-            raise ValueError("groups holds a label beyond the int64 range")
-        labels = torch.as_tensor(np.ascontiguousarray(arr.astype(np.int64)))
-    if labels.dim() != 1:
-        raise ValueError(f"groups must be 1-D (one label per stored row), got shape {tuple(labels.shape)}")
-    return labels
-
-
 def frechet_distance_per_group(x: AudioMetricsData, y: AudioMetricsData, groups, device=None):
     """Frechet distance of every group of x's stored rows, each on its own, against y's full-set statistics (the
     "individual" / per-song score of the evaluation toolkits).  `groups`: one integer label per stored row of x (numpy or
@@ -161,16 +144,7 @@ def frechet_distance_per_group(x: AudioMetricsData, y: AudioMetricsData, groups,
     while its other stopping rules (1 converged, 2 trace stalled, 3 zero product) are regular ends there; a non-finite value
     raises on either route.  The dual form is
     the dust-free definition for a group with fewer rows than dimensions, so no rank-deficiency warning is raised here."""
-    rows = getattr(x, "embeddings", None)
-    n = int(rows.shape[0]) if rows is not None else 0
-    if rows is None or n == 0:
-        raise ValueError(f"frechet_distance_per_group scores the stored rows of its first argument, which keeps none "
-                         f"(store_embeddings={getattr(x, 'store_embeddings', None)})")
-    labels = _group_labels(groups)
-    if labels.numel() == 0:
-        raise ValueError("groups is empty")
-    if labels.numel() != n:
-        raise ValueError(f"groups holds {labels.numel()} labels for {n} stored rows (one label per row)")
+    rows, n, labels = labelled_rows(x, groups, "frechet_distance_per_group", "its first argument")
     d = int(rows.shape[1])
     d_y = int(ensure_tensor(y.mean).numel())
     if d_y != d:
@@ -184,11 +158,7 @@ def frechet_distance_per_group(x: AudioMetricsData, y: AudioMetricsData, groups,
     rows = ops.as_rows(rows.to(device))
     mu_y, cov_y = (ensure_tensor(t).to(device, torch.float64) for t in (y.mean, y.cov))
     mu_y = mu_y.reshape(-1)
-    labels = labels.to(device, torch.int64)
-    sorted_labels, order = torch.sort(labels, stable=True)
-    uniq, counts = torch.unique_consecutive(sorted_labels, return_counts=True)
-    host = torch.stack([uniq, counts]).cpu().numpy()                       # the one read-back in front of the kernels
-    group_labels, sizes = host[0].copy(), host[1].astype(np.int64)
+    order, counts, group_labels, sizes = sort_into_groups(labels.to(device, torch.int64))
     nb = len(sizes)
     cap = ops.frechet_groups_max_rows()
     small = sizes <= cap

@@ -18,7 +18,7 @@ import torch
 
 from .. import hip_ops as ops
 from ..data import AudioMetricsData
-from .fad import _group_labels
+from ._groups import labelled_rows, sort_into_groups
 
 KAD_SCALE = 100.0
 CACHE_ATTR = "_kad_cache"         # on the reference AudioMetricsData; NOT part of serialize(): the file layout stays as it is
@@ -64,21 +64,17 @@ def _rows_of(data, name):
     return rows
 
 
-def kernel_audio_distance(x: AudioMetricsData, y: AudioMetricsData, bandwidth=None, scale=KAD_SCALE):
-    """KAD of candidate set `x` against reference set `y`.  bandwidth=None: the median pairwise distance of `y`; a number
-    fixes it.  Returns {"kad": scale * mmd^2, "kad_mmd2": mmd^2, "kad_bandwidth": bw}."""
-    ex, ey = _rows_of(x, "candidate"), _rows_of(y, "reference")
-    if ex.shape[1] != ey.shape[1]:
-        raise ValueError(f"feature widths differ: {ex.shape[1]} and {ey.shape[1]}")
-    gamma = None
+def _resolve_bandwidth(bandwidth, y, ey):
+    """(cache, bw, gamma, bw2_dev) for `bandwidth` against the reference-side cache of y.  A number fixes bw and gamma and
+    leaves bw2_dev None; None takes the median squared distance of the reference rows ey as the device scalar bw2_dev
+    (computed once per content of y), and gamma stays None until a result has been read back once."""
+    bw = gamma = bw2_dev = None
     if bandwidth is not None:
         bw = float(bandwidth)
         if not math.isfinite(bw) or bw <= 0.0:
             raise ValueError(f"bandwidth={bandwidth!r} must be a finite positive number")
         gamma = 1.0 / (2.0 * bw * bw)
-    n, m = int(ex.shape[0]), int(ey.shape[0])
     cache = reference_cache(y)
-    bw2_dev = None
     if gamma is None:
         if cache.bw2 is None:
             cache.bw2 = ops.pairwise_select_sq(ey)
@@ -86,6 +82,30 @@ def kernel_audio_distance(x: AudioMetricsData, y: AudioMetricsData, bandwidth=No
         if cache.bw2_host is not None:                     # the bits the device forms from the same float32: 0.5 / (double)bw2
             _check_bandwidth(cache.bw2_host)
             gamma = 0.5 / cache.bw2_host
+    return cache, bw, gamma, bw2_dev
+
+
+def _finish_bandwidth(cache, bw, gamma, bw2_dev, bw2_v, fresh_syy):
+    """After the read-back: the bandwidth the device used (bw2_v, where it came from bw2_dev) goes into the cache and is
+    checked, and a freshly computed Syy is stored under the gamma it belongs to.  Returns bw."""
+    if bw2_dev is not None:
+        cache.bw2_host = bw2_v
+        _check_bandwidth(bw2_v)
+        gamma = 0.5 / bw2_v
+        bw = math.sqrt(bw2_v)
+    if fresh_syy is not None:
+        cache.syy[_gamma_bits(gamma)] = fresh_syy
+    return bw
+
+
+def kernel_audio_distance(x: AudioMetricsData, y: AudioMetricsData, bandwidth=None, scale=KAD_SCALE):
+    """KAD of candidate set `x` against reference set `y`.  bandwidth=None: the median pairwise distance of `y`; a number
+    fixes it.  Returns {"kad": scale * mmd^2, "kad_mmd2": mmd^2, "kad_bandwidth": bw}."""
+    ex, ey = _rows_of(x, "candidate"), _rows_of(y, "reference")
+    if ex.shape[1] != ey.shape[1]:
+        raise ValueError(f"feature widths differ: {ex.shape[1]} and {ey.shape[1]}")
+    n, m = int(ex.shape[0]), int(ey.shape[0])
+    cache, bw, gamma, bw2_dev = _resolve_bandwidth(bandwidth, y, ey)
     syy = cache.syy.get(_gamma_bits(gamma)) if gamma is not None else None
     blocks = ops.MMD_XX | ops.MMD_XY | (0 if syy is not None else ops.MMD_YY)
     if bw2_dev is not None:
@@ -97,13 +117,7 @@ def kernel_audio_distance(x: AudioMetricsData, y: AudioMetricsData, bandwidth=No
         syy = sums[1].clone()
     tail = bw2_dev.to(torch.float64) if bw2_dev is not None else torch.zeros((), dtype=torch.float64, device=sums.device)
     sxx, sxy, syy_v, bw2_v = torch.stack([sums[0], sums[2], syy, tail]).cpu().tolist()       # the one read-back
-    if bw2_dev is not None:
-        cache.bw2_host = bw2_v
-        _check_bandwidth(bw2_v)
-        gamma = 0.5 / bw2_v
-        bw = math.sqrt(bw2_v)
-    if fresh_syy:
-        cache.syy[_gamma_bits(gamma)] = syy
+    bw = _finish_bandwidth(cache, bw, gamma, bw2_dev, bw2_v, syy if fresh_syy else None)
     mmd2 = sxx / (n * (n - 1.0)) + syy_v / (m * (m - 1.0)) - 2.0 * sxy / (float(n) * m)
     return {"kad": float(scale) * mmd2, "kad_mmd2": mmd2, "kad_bandwidth": bw}
 
@@ -134,44 +148,17 @@ def kernel_audio_distance_per_group(x: AudioMetricsData, y: AudioMetricsData, gr
     ascending, "group_sizes": int64 [B], "kad_bandwidth": float}; return_rows=True adds "row_cross_mean": f64 [n] in STORED
     row order, c_i / m = the reference's kernel density at each candidate row.  A group of one row gets NaN and the call
     one RuntimeWarning."""
-    rows = getattr(x, "embeddings", None)
-    n = int(rows.shape[0]) if rows is not None else 0
-    if rows is None or n == 0:
-        raise ValueError(f"kernel_audio_distance_per_group scores the stored rows of its candidate set, which keeps none "
-                         f"(store_embeddings={getattr(x, 'store_embeddings', None)})")
-    labels = _group_labels(groups)
-    if labels.numel() == 0:
-        raise ValueError("groups is empty")
-    if labels.numel() != n:
-        raise ValueError(f"groups holds {labels.numel()} labels for {n} stored rows (one label per row)")
+    rows, n, labels = labelled_rows(x, groups, "kernel_audio_distance_per_group", "its candidate set")
     ey = _rows_of(y, "reference")
     if rows.dtype == torch.float64:
         raise NotImplementedError("kernel_audio_distance_per_group: the candidate set holds float64 rows; the float64 "
                                   "matrix-core form of the kernel sums is not implemented")
     if rows.shape[1] != ey.shape[1]:
         raise ValueError(f"feature widths differ: {rows.shape[1]} and {ey.shape[1]}")
-    gamma = None
-    if bandwidth is not None:
-        bw = float(bandwidth)
-        if not math.isfinite(bw) or bw <= 0.0:
-            raise ValueError(f"bandwidth={bandwidth!r} must be a finite positive number")
-        gamma = 1.0 / (2.0 * bw * bw)
     m = int(ey.shape[0])
-    labels = labels.to(rows.device, torch.int64)
-    sorted_labels, order = torch.sort(labels, stable=True)
-    uniq, counts = torch.unique_consecutive(sorted_labels, return_counts=True)
-    host = torch.stack([uniq, counts]).cpu().numpy()                       # the one read-back in front of the kernels
-    group_labels, sizes = host[0].copy(), host[1].astype(np.int64)
+    cache, bw, gamma, bw2_dev = _resolve_bandwidth(bandwidth, y, ey)
+    order, _, group_labels, sizes = sort_into_groups(labels.to(rows.device, torch.int64))
     offs = np.concatenate([[0], np.cumsum(sizes)]).tolist()
-    cache = reference_cache(y)
-    bw2_dev = None
-    if gamma is None:
-        if cache.bw2 is None:
-            cache.bw2 = ops.pairwise_select_sq(ey)
-        bw2_dev = cache.bw2
-        if cache.bw2_host is not None:                     # the bits the device forms from the same float32: 0.5 / (double)bw2
-            _check_bandwidth(cache.bw2_host)
-            gamma = 0.5 / cache.bw2_host
     width = {"bw2": bw2_dev} if bw2_dev is not None else {"gamma": gamma}
     syy = cache.syy.get(_gamma_bits(gamma)) if gamma is not None else None
     fresh_syy = syy is None
@@ -189,13 +176,7 @@ def kernel_audio_distance_per_group(x: AudioMetricsData, y: AudioMetricsData, gr
     check()
     nb = len(sizes)
     syy_v, bw2_v = float(flat[2 * nb]), float(flat[2 * nb + 1])
-    if bw2_dev is not None:
-        cache.bw2_host = bw2_v
-        _check_bandwidth(bw2_v)
-        gamma = 0.5 / bw2_v
-        bw = math.sqrt(bw2_v)
-    if fresh_syy:
-        cache.syy[_gamma_bits(gamma)] = syy
+    bw = _finish_bandwidth(cache, bw, gamma, bw2_dev, bw2_v, syy if fresh_syy else None)
     sums = flat[:2 * nb].reshape(nb, 2)
     kad, mmd2 = combine_group_sums(sums[:, 0], sums[:, 1], sizes, syy_v, m, scale)
     out = {"kad_per_group": kad, "kad_mmd2_per_group": mmd2, "group_labels": group_labels, "group_sizes": sizes, "kad_bandwidth": bw}
