@@ -97,8 +97,9 @@ class AudioMetrics:
             raise NotImplementedError('metric "kad" sweeps the stored rows of one device (whole-set kernel sums and a median over '
                                       "all reference pairs); it is not implemented for row-sharded sets (process_group=)")
         if n_pca is not None and "kad" in metrics:
-            raise NotImplementedError('metric "kad" takes float32 rows; the PCA projection (n_pca=) hands on float64 rows, whose '
-                                      "matrix-core form of the select and the kernel sums is not implemented")
+            raise NotImplementedError('metric "kad" is not enabled behind the PCA projection (n_pca=) yet: the projection hands on '
+                                      "float64 rows, which kernel_audio_distance takes on their own (two float64 sets), but "
+                                      "this front-end combination has no tests of its own")
         self._devices = _visible_devices(device_indices, process_group is not None, embedder)
         self.device = self._devices[0]                 # where statistics, stored rows and metric kernels live
         self._group = process_group

@@ -668,33 +668,53 @@ def kd_rbf(x, y, idx1, idx2, sigma):
 MMD_XX, MMD_YY, MMD_XY = 1, 2, 4                       # enum am_mmd_block
 
 
+def _kad_kind(what, *sets):
+    """"f64" when every set holds float64 rows (the *_f64 entry points of the Kernel Audio Distance calls), "f32" when none
+    does; a mixed pair is refused before anything touches the tensors."""
+    wide = [is_f64(t) for t in sets]
+    if any(wide) and not all(wide):
+        raise NotImplementedError(f"{what} takes float32 rows, or float64 rows in BOTH sets (a mixed pair is not implemented: "
+                                  "convert one side)")
+    return "f64" if all(wide) else "f32"
+
+
+def _kad_matrix(kind, e, name):
+    """(the matrix form the `kind` entry points take, its leading dimension)"""
+    if kind == "f64":
+        e = as_matrix64(e, name)
+        return e, _ld64(e)
+    e = as_matrix(e, name)
+    return e, _ld(e)
+
+
 def pairwise_select_sq(x, rank=None):
     """The element of 0-based `rank` (None: the lower median, torch.median's convention) among the float32 squared
     distances of the N (N - 1) / 2 unordered row pairs of x, as a 0-dim float32 DEVICE tensor: an exact radix select over
-    recomputed Gram tiles (am_pairwise_select_f32), stream-ordered, no host synchronisation."""
+    recomputed Gram tiles (am_pairwise_select_f32; float64 rows: am_pairwise_select_f64, every distance in f64 and the
+    result its float32 rounding), stream-ordered, no host synchronisation."""
     lib = _lib.load()
-    if is_f64(x):
-        raise NotImplementedError("pairwise_select_sq takes float32 rows (the float64 matrix-core form is not implemented)")
-    x = as_matrix(x, "x")
+    kind = _kad_kind("pairwise_select_sq", x)
+    x, ld = _kad_matrix(kind, x, "x")
     n, d = x.shape
     out = torch.empty((), dtype=torch.float32, device=x.device)
-    nb = lib.am_pairwise_select_workspace_bytes(n, d)
+    query = lib.am_pairwise_select_f64_workspace_bytes if kind == "f64" else lib.am_pairwise_select_workspace_bytes
+    nb = query(n, d)
     ws = _workspace(nb, x.device)
-    _call(lib, "am_pairwise_select_f32", x.device, _ptr(x), n, _ld(x), d, -1 if rank is None else int(rank), _ptr(out),
+    _call(lib, "am_pairwise_select_" + kind, x.device, _ptr(x), n, ld, d, -1 if rank is None else int(rank), _ptr(out),
           _ptr(ws), nb)
     return out
 
 
 def mmd_rbf_sums(x, y, bw2=None, gamma=None, blocks=7, out=None):
-    """float64[3] device tensor {Sxx, Syy, Sxy} of K = exp(-|a - b|^2 gamma) over the whole sets (am_mmd_rbf_f32): Sxx / Syy
-    over ordered pairs i != j, Sxy over all pairs.  `bw2`: a float32 DEVICE scalar (gamma = 0.5 / bw2 is formed on the
-    device - the output of pairwise_select_sq, no host round trip) or `gamma`: a number.  Only the slots named by `blocks`
-    (MMD_XX | MMD_YY | MMD_XY) are written; the others keep what `out` held (NaN in a fresh tensor)."""
+    """float64[3] device tensor {Sxx, Syy, Sxy} of K = exp(-|a - b|^2 gamma) over the whole sets (am_mmd_rbf_f32; both sets
+    float64: am_mmd_rbf_f64): Sxx / Syy over ordered pairs i != j, Sxy over all pairs.  `bw2`: a float32 DEVICE scalar
+    (gamma = 0.5 / bw2 is formed on the device - the output of pairwise_select_sq, no host round trip) or `gamma`: a number.
+    Only the slots named by `blocks` (MMD_XX | MMD_YY | MMD_XY) are written; the others keep what `out` held (NaN in a
+    fresh tensor)."""
     lib = _lib.load()
-    if is_f64(x) or is_f64(y):
-        raise NotImplementedError("mmd_rbf_sums takes float32 rows (the float64 matrix-core form is not implemented)")
+    kind = _kad_kind("mmd_rbf_sums", x, y)
     bw2_arg, gamma_arg = _bandwidth_args(bw2, gamma)
-    x, y = as_matrix(x, "x"), as_matrix(y, "y")
+    (x, ldx), (y, ldy) = _kad_matrix(kind, x, "x"), _kad_matrix(kind, y, "y")
     dev = _same_device(x, y)
     if x.shape[1] != y.shape[1]:
         raise ValueError(f"feature widths differ: {x.shape[1]} and {y.shape[1]}")
@@ -703,15 +723,17 @@ def mmd_rbf_sums(x, y, bw2=None, gamma=None, blocks=7, out=None):
     elif not (out.is_cuda and out.dtype == torch.float64 and out.numel() == 3 and out.is_contiguous()):
         raise ValueError("out must be a contiguous float64[3] device tensor")
     blocks = int(blocks)
-    nb = lib.am_mmd_rbf_workspace_bytes(x.shape[0], y.shape[0], x.shape[1], blocks)
+    query = lib.am_mmd_rbf_f64_workspace_bytes if kind == "f64" else lib.am_mmd_rbf_workspace_bytes
+    nb = query(x.shape[0], y.shape[0], x.shape[1], blocks)
     ws = _workspace(nb, dev)
-    _call(lib, "am_mmd_rbf_f32", dev, _ptr(x), x.shape[0], _ld(x), _ptr(y), y.shape[0], _ld(y), x.shape[1],
+    _call(lib, "am_mmd_rbf_" + kind, dev, _ptr(x), x.shape[0], ldx, _ptr(y), y.shape[0], ldy, x.shape[1],
           bw2_arg, gamma_arg, blocks, _ptr(out), _ptr(ws), nb)
     return out
 
 
 def mmd_rbf_group_sums(x, idx, offsets, y, bw2=None, gamma=None, rows=False):
-    """Per-group Gaussian kernel sums in one library call (am_mmd_rbf_groups_f32): group b is the rows
+    """Per-group Gaussian kernel sums in one library call (am_mmd_rbf_groups_f32; both sets float64:
+    am_mmd_rbf_groups_f64): group b is the rows
     x[idx[offsets[b]:offsets[b + 1]]] (idx: int64 device tensor, or None for the rows in stored order; offsets: B + 1 host
     integers starting at 0, strictly increasing; any group size), each against the whole reference y.  `bw2` / `gamma` as
     for mmd_rbf_sums.  Nothing waits for the device: returns (out_groups, check), or (out_groups, out_rows, check) with
@@ -720,10 +742,9 @@ def mmd_rbf_group_sums(x, idx, offsets, y, bw2=None, gamma=None, rows=False):
     order, and check() the one host read of the workspace's flag word, which raises ValueError for an index outside
     [0, N1) (the kernels never dereference it)."""
     lib = _lib.load()
-    if is_f64(x) or is_f64(y):
-        raise NotImplementedError("mmd_rbf_group_sums takes float32 rows (the float64 matrix-core form is not implemented)")
+    kind = _kad_kind("mmd_rbf_group_sums", x, y)
     bw2_arg, gamma_arg = _bandwidth_args(bw2, gamma)
-    x, y = as_matrix(x, "x"), as_matrix(y, "y")
+    (x, ldx), (y, ldy) = _kad_matrix(kind, x, "x"), _kad_matrix(kind, y, "y")
     dev = _same_device(x, y)
     n, d = x.shape
     if d != y.shape[1]:
@@ -732,11 +753,12 @@ def mmd_rbf_group_sums(x, idx, offsets, y, bw2=None, gamma=None, rows=False):
     idx = _group_index(idx, offs[-1], x)
     out_groups = torch.empty((b, 2), dtype=torch.float64, device=dev)
     out_rows = torch.empty((offs[-1], 2), dtype=torch.float64, device=dev) if rows else None
-    nb = lib.am_mmd_rbf_groups_workspace_bytes(offs[-1], b, y.shape[0], d)
+    query = lib.am_mmd_rbf_groups_f64_workspace_bytes if kind == "f64" else lib.am_mmd_rbf_groups_workspace_bytes
+    nb = query(offs[-1], b, y.shape[0], d)
     ws = _workspace(nb, dev)
     null = ctypes.c_void_p(None)
-    _call(lib, "am_mmd_rbf_groups_f32", dev, _ptr(x), n, _ld(x), _ptr(idx) if idx is not None else null,
-          ctypes.cast(host_offs, ctypes.c_void_p), b, _ptr(y), y.shape[0], _ld(y), d, bw2_arg, gamma_arg, _ptr(out_groups),
+    _call(lib, "am_mmd_rbf_groups_" + kind, dev, _ptr(x), n, ldx, _ptr(idx) if idx is not None else null,
+          ctypes.cast(host_offs, ctypes.c_void_p), b, _ptr(y), y.shape[0], ldy, d, bw2_arg, gamma_arg, _ptr(out_groups),
           _ptr(out_rows) if rows else null, _ptr(ws), nb)
     check = _index_check(ws, idx, n, "group rows")
     return (out_groups, out_rows, check) if rows else (out_groups, check)

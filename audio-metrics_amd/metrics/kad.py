@@ -1,7 +1,8 @@
 """Kernel Audio Distance (Chung et al. 2025, "KAD: No More FAD!"): the unbiased MMD^2 between the WHOLE candidate set and
 the WHOLE reference set under a Gaussian kernel whose bandwidth is the median pairwise distance of the reference set.
 
-  d2(a, b) = max((|a|^2 + |b|^2) - 2 a.b, 0)            f64, f64 norms, f32 matrix-core dot product
+  d2(a, b) = max((|a|^2 + |b|^2) - 2 a.b, 0)            f64, f64 norms, f32 matrix-core dot product (float32 rows);
+                                                         two float64 sets: the f64 matrix cores, every step in f64
   bw^2     = rn32(lower median of d2 over the m (m - 1) / 2 unordered reference pairs)        (ops.pairwise_select_sq)
   k(a, b)  = exp(-d2(a, b) / (2 bw^2))                                                        (ops.mmd_rbf_sums)
   mmd^2    = Sxx / (n (n - 1)) + Syy / (m (m - 1)) - 2 Sxy / (n m),     kad = scale * mmd^2
@@ -58,10 +59,16 @@ def _rows_of(data, name):
     if rows.shape[0] < 2:
         raise ValueError(f"kernel_audio_distance needs at least 2 rows in the {name} set (it holds {rows.shape[0]}): the "
                          "unbiased MMD^2 divides by n (n - 1)")
-    if rows.dtype == torch.float64:
-        raise NotImplementedError(f"kernel_audio_distance: the {name} set holds float64 rows; the float64 matrix-core form "
-                                  "of the select and of the kernel sums is not implemented")
     return rows
+
+
+def _same_row_type(what, ex, ey):
+    """float32 rows in both sets (the f32 tile engine) or float64 rows in both (the f64 matrix-core forms: every step in
+    f64, the bandwidth still the float32 rounding of the f64 median); a mixed pair is refused before any device call."""
+    for rows, name, other in ((ex, "candidate", ey), (ey, "reference", ex)):
+        if rows.dtype == torch.float64 and other.dtype != torch.float64:
+            raise NotImplementedError(f"{what}: the {name} set holds float64 rows and the other set {other.dtype} rows; both "
+                                      "sets must hold float32 rows or both float64 rows (a mixed pair is not implemented)")
 
 
 def _resolve_bandwidth(bandwidth, y, ey):
@@ -102,6 +109,7 @@ def kernel_audio_distance(x: AudioMetricsData, y: AudioMetricsData, bandwidth=No
     """KAD of candidate set `x` against reference set `y`.  bandwidth=None: the median pairwise distance of `y`; a number
     fixes it.  Returns {"kad": scale * mmd^2, "kad_mmd2": mmd^2, "kad_bandwidth": bw}."""
     ex, ey = _rows_of(x, "candidate"), _rows_of(y, "reference")
+    _same_row_type("kernel_audio_distance", ex, ey)
     if ex.shape[1] != ey.shape[1]:
         raise ValueError(f"feature widths differ: {ex.shape[1]} and {ey.shape[1]}")
     n, m = int(ex.shape[0]), int(ey.shape[0])
@@ -150,9 +158,7 @@ def kernel_audio_distance_per_group(x: AudioMetricsData, y: AudioMetricsData, gr
     one RuntimeWarning."""
     rows, n, labels = labelled_rows(x, groups, "kernel_audio_distance_per_group", "its candidate set")
     ey = _rows_of(y, "reference")
-    if rows.dtype == torch.float64:
-        raise NotImplementedError("kernel_audio_distance_per_group: the candidate set holds float64 rows; the float64 "
-                                  "matrix-core form of the kernel sums is not implemented")
+    _same_row_type("kernel_audio_distance_per_group", rows, ey)
     if rows.shape[1] != ey.shape[1]:
         raise ValueError(f"feature widths differ: {rows.shape[1]} and {ey.shape[1]}")
     m = int(ey.shape[0])

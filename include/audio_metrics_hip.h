@@ -324,6 +324,41 @@ int am_mmd_rbf_groups_f32(const float* X, int64_t N1, int64_t ldx,
                           void* ws, size_t ws_bytes, am_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Kernel Audio Distance on float64 rows (csrc/kad_f64.hip, the f64 tile engine of the other *_f64 entry points: 64 x 64 tiles
+ * on v_mfma_f64_16x16x4_f64).  The three calls above with `const double*` rows and the same argument lists; taken when BOTH
+ * sets hold float64 rows.  Every step is f64: squared norms, the matrix-core dot product,
+ *   select:  d2 = max(fma(-2, dot, |a|^2 + |b|^2), 0), a NaN distance (a non-finite row) carried as +inf
+ *   sums:    the same d2 with a NaN left in place, k = exp(-d2 gamma): as in the f32 forms a non-finite row makes the sums
+ *            it takes part in NaN.
+ * Rows need no alignment (8-byte loads; any ld >= D) and no buffer descriptor spans a matrix: the 4 GiB rule of the f32
+ * forms does not apply (N, N1, N2 < 2^31).
+ *
+ * am_pairwise_select_f64: the contract of am_pairwise_select_f32 - *out_d2 is a FLOAT32, rn32 of the f64 order statistic
+ *   (rounding is monotone: select-then-round = round-then-select), keys bits(rn32(d2)) with NaN and overflow +inf, three
+ *   radix passes of 11 / 10 / 10 bits over the upper-triangular tiles, bin totals in 64 bits, no host synchronisation.
+ * am_mmd_rbf_f64: the contract of am_mmd_rbf_f32 (`blocks`, bw2_dev - still a DEVICE float: gamma = 0.5 / (double)*bw2_dev
+ *   is formed on the device -, one f64 partial per workgroup summed in a fixed order: same input, same bits).
+ * am_mmd_rbf_groups_f64: the contract of am_mmd_rbf_groups_f32 (list protocol, flag word in the first 8 bytes of `ws`, an
+ *   out-of-range index counts as a zero row, out_groups / out_rows, results that depend on the list order only, same bits
+ *   on every call); tiles hold 64 list positions; D <= 8192; n_total < 2^30; N2 >= 2.
+ * ------------------------------------------------------------------------- */
+size_t am_pairwise_select_f64_workspace_bytes(int64_t N, int D);
+int am_pairwise_select_f64(const double* X, int64_t N, int64_t ld, int D, int64_t rank,
+                           float* out_d2, void* ws, size_t ws_bytes, am_stream_t stream);
+size_t am_mmd_rbf_f64_workspace_bytes(int64_t N1, int64_t N2, int D, unsigned blocks);
+int am_mmd_rbf_f64(const double* X, int64_t N1, int64_t ldx,
+                   const double* Y, int64_t N2, int64_t ldy, int D,
+                   const float* bw2_dev, double gamma, unsigned blocks,
+                   double* out_sums, void* ws, size_t ws_bytes, am_stream_t stream);
+size_t am_mmd_rbf_groups_f64_workspace_bytes(int64_t n_total, int B, int64_t N2, int D);
+int am_mmd_rbf_groups_f64(const double* X, int64_t N1, int64_t ldx,
+                          const int64_t* idx, const int64_t* offsets, int B,
+                          const double* Y, int64_t N2, int64_t ldy, int D,
+                          const float* bw2_dev, double gamma,
+                          double* out_groups, double* out_rows,
+                          void* ws, size_t ws_bytes, am_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * A9  k-NN radii                                reference: prdc.py:4-14, data.py:60-66
  *   out_r[i] = (k+1)-th smallest Euclidean distance from row i of X to the M
  *   rows of Y (Y == X for the reference's self-distance use; a multi-GPU

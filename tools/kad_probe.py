@@ -3,6 +3,8 @@ kernel_audio_distance against a cached reference, and - at a size torch.pdist ca
 metric for comparison of time and value.
 
     python tools/kad_probe.py > profiles/kad/probe.txt
+    python tools/kad_probe.py --f64 > profiles/kad_f64/probe.txt      (the three float64 entry points at 100 000 x 64 float64
+                                                                       rows beside the f32 ones on the same values narrowed)
 """
 import argparse
 import os
@@ -17,6 +19,7 @@ from audio_metrics_amd import hip_ops as ops                            # noqa: 
 
 DEV = torch.device("cuda", 0)
 F32_MFMA_PEAK = 157.3e12                                                # flop/s, dense f32 matrix cores of one MI355X
+F64_MFMA_PEAK = 78.6e12                                                 # flop/s, f64 matrix cores (v_mfma_f64_16x16x4_f64)
 
 
 def rows(seed, n, d, shift):
@@ -67,14 +70,41 @@ def torch_kad(x, y, block=4096):
     return mmd2, bw2, how
 
 
+def probe_f64(n, d, groups, reps):
+    """The three float64 entry points beside the f32 ones on the same values narrowed: select, the three sums, and the
+    per-group sums of `groups` equal groups.  No time is a pass / fail condition."""
+    y64, x64 = rows(1, n, d, 0.5).double(), rows(2, n, d, 0.55).double()
+    y64, x64 = y64 / y64.norm(dim=1, keepdim=True), x64 / x64.norm(dim=1, keepdim=True)
+    y32, x32 = y64.float(), x64.float()
+    half, full = n * (n - 1) / 2 * 2 * d, 2.0 * n * n * d
+    offs = [n * b // groups for b in range(groups + 1)]
+    for kind, x, y, peak in (("f64", x64, y64, F64_MFMA_PEAK), ("f32", x32, y32, F32_MFMA_PEAK)):
+        t, bw2 = timed(lambda: ops.pairwise_select_sq(y), reps)
+        print(f"{kind} select        {n} x {d}: {t:9.2f} ms  ({100 * 3 * half / peak / (t * 1e-3):.0f} % of the {kind} matrix peak over 3 passes); "
+              f"median d2 {bw2.item():.9f}")
+        for name, blocks, flop in (("sums YY", ops.MMD_YY, half), ("sums XY", ops.MMD_XY, full), ("sums all", 7, 2 * half + full)):
+            t, out = timed(lambda: ops.mmd_rbf_sums(x, y, bw2=bw2, blocks=blocks), reps)
+            print(f"{kind} {name:13s} {n} x {d}: {t:9.2f} ms  ({100 * flop / peak / (t * 1e-3):.0f} % of the {kind} matrix peak)  "
+                  f"{[float(v) for v in out.cpu()]}")
+        t, res = timed(lambda: ops.mmd_rbf_group_sums(x, None, offs, y, bw2=bw2), reps)
+        res[-1]()
+        print(f"{kind} group sums    {n} x {d} in {groups} groups: {t:9.2f} ms  ({100 * full / peak / (t * 1e-3):.0f} % of the {kind} matrix peak, "
+              f"cross pass alone); sum Sxy {float(res[0][:, 1].sum()):.9e}")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--f64", action="store_true", help="time the float64 entry points at --rows x 64 beside the f32 ones")
+    ap.add_argument("--groups", type=int, default=1000)
     ap.add_argument("--rows", type=int, default=100_000)
     ap.add_argument("--small", type=int, default=1_000)
     ap.add_argument("--torch-rows", type=int, default=20_000)
     ap.add_argument("--reps", type=int, default=2)
     args = ap.parse_args()
     print(f"# {torch.cuda.get_device_name(0)}; events, warm, mean of {args.reps}")
+    if args.f64:
+        probe_f64(args.rows, 64, args.groups, args.reps)
+        return
     for d in (512, 128):
         n = args.rows
         y, x, xs = rows(1, n, d, 0.5), rows(2, n, d, 0.55), rows(3, args.small, d, 0.55)
