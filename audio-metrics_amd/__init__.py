@@ -15,6 +15,7 @@ from .metrics.kad import kernel_audio_distance                                # 
 from .metrics.kad import kernel_audio_distance_per_group                      # noqa: F401
 from .metrics.prdc import prdc, nearest_neighbour_distances                   # noqa: F401
 from .metrics.neighbors import nearest_neighbors                              # noqa: F401
+from .metrics.mauve import kmeans, mauve_score, mauve_from_histograms         # noqa: F401
 from .metrics.apa import apa, apa_compute_d_x_xp                              # noqa: F401
 
 from .embed import ItemCategory, embedding_pipeline                            # noqa: F401

@@ -874,6 +874,69 @@ def knn_search_chunks(n, m, d, k):
     return int(_lib.load().am_knn_search_chunks(int(n), int(m), int(d), int(k)))
 
 
+# ---- k-means: the two halves of a Lloyd iteration (csrc/kmeans.hip) ----
+def _kmeans_check(what, x, c):
+    if is_f64(x) or is_f64(c):
+        raise NotImplementedError(f"{what} takes float32 rows (the float64 matrix-core form is not implemented)")
+    if x.dim() != 2 or c.dim() != 2:
+        raise ValueError(f"rows and centroids must be 2-D, got shapes {tuple(x.shape)} and {tuple(c.shape)}")
+    if x.shape[1] != c.shape[1]:
+        raise ValueError(f"feature widths differ: {x.shape[1]} and {c.shape[1]}")
+    if c.shape[0] < 1:
+        raise ValueError(f"{what} needs at least one centroid (K={c.shape[0]})")
+    if x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError(f"{what} needs rows (got shape {tuple(x.shape)})")
+
+
+def kmeans_assign(x, c):
+    """The nearest row of c for every row of x (am_kmeans_assign_f32): (labels int64 [N], d2 float32 [N], inertia float64
+    0-d) as device tensors, stream-ordered, nothing waits for the device.  labels and d2 have the bits of
+    knn_search(x, c, 1, squared=True); ties go to the smallest centroid index; a row without a finite distance is
+    (-1, +inf) and is left out of inertia, the f64 sum of d2 added in a fixed order."""
+    _kmeans_check("kmeans_assign", x, c)
+    lib = _lib.load()
+    x, c = as_matrix(x, "x"), as_matrix(c, "c")
+    dev = _same_device(x, c)
+    n, d = x.shape
+    k = c.shape[0]
+    labels = torch.empty(n, dtype=torch.int64, device=dev)
+    d2 = torch.empty(n, dtype=torch.float32, device=dev)
+    inertia = torch.empty((), dtype=torch.float64, device=dev)
+    nb = lib.am_kmeans_assign_workspace_bytes(n, k, d)
+    ws = _workspace(nb, dev)
+    _call(lib, "am_kmeans_assign_f32", dev, _ptr(x), n, _ld(x), _ptr(c), k, _ld(c), d, _ptr(labels), _ptr(d2), _ptr(inertia),
+          _ptr(ws), nb)
+    return labels, d2, inertia
+
+
+def kmeans_update(x, labels, c_old):
+    """The mean of the rows of x under every label (am_kmeans_update_f32): (c_new float32 [K, D], counts int64 [K]) as
+    device tensors, stream-ordered, nothing waits for the device.  Sums run in f64 in ascending row order and are rounded to
+    f32 once; a label without rows keeps its row of c_old bit for bit and counts 0; labels of -1 (kmeans_assign's "no finite
+    distance") are ignored.  The rows are sorted by label on the device (torch.sort(stable=True), torch.searchsorted)."""
+    _kmeans_check("kmeans_update", x, c_old)
+    if not torch.is_tensor(labels) or labels.dim() != 1 or labels.shape[0] != x.shape[0] or labels.dtype != torch.int64:
+        raise ValueError(f"labels must be an int64 tensor with one entry per row ({x.shape[0]}), got "
+                         f"{getattr(labels, 'dtype', type(labels).__name__)} {tuple(getattr(labels, 'shape', ()))}")
+    lib = _lib.load()
+    x, c_old = as_matrix(x, "x"), as_matrix(c_old, "c_old")
+    _require_cuda(labels, "labels")
+    dev = _same_device(x, c_old, labels)
+    n, d = x.shape
+    k = c_old.shape[0]
+    labels = labels.contiguous()
+    ordered, order = torch.sort(labels, stable=True)                       # rows with label -1 come first
+    offsets = torch.searchsorted(ordered, torch.arange(k + 1, dtype=torch.int64, device=dev))
+    ld = (d + 3) // 4 * 4
+    c_new = torch.empty((k, ld), dtype=torch.float32, device=dev)[:, :d]
+    counts = torch.empty(k, dtype=torch.int64, device=dev)
+    nb = lib.am_kmeans_update_workspace_bytes(n, k, d)
+    ws = _workspace(nb, dev)
+    _call(lib, "am_kmeans_update_f32", dev, _ptr(x), n, _ld(x), d, _ptr(labels), _ptr(order), _ptr(offsets), k, _ptr(c_old),
+          _ld(c_old), _ptr(c_new), ld, _ptr(counts), _ptr(ws), nb)
+    return c_new, counts
+
+
 # ---- partitioned symmetric k-NN (multi-GPU, every rank holds the full set) ----
 def knn_path(n, m, d, k, self_distance=True):
     """0 exact general kernel, 1 exact symmetric kernel, 2 / 3 f16 filter + exact verification (128 / 256-row engine)."""

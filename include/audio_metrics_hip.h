@@ -405,6 +405,40 @@ int am_knn_search_f32(const float* X, int64_t N, int64_t ldx, const float* Y, in
                       void* ws, size_t ws_bytes, am_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * K-MEANS, the two halves of a Lloyd iteration (csrc/kmeans.hip)              no counterpart in the reference
+ *   Every pointer below is a DEVICE pointer, `inertia` included: an iteration needs no read-back.  Everything is validated
+ *   before the first HIP call; the calls are asynchronous.  No floating-point atomics: two calls return the same bits.
+ *
+ *   ASSIGN.  labels[i] = the nearest of the K rows of C (int64), d2[i] = its squared distance - the tile kernel and the
+ *   arithmetic of am_knn_search_f32 at k = 1, squared: d2 = max(fmaf(-2, <x, c>, |x|^2 + |c|^2), 0) in f32 with the same
+ *   row norms and inner order, the same bits.  Ties go to the SMALLEST centroid index whatever the chunking.  A row
+ *   without a finite distance (a non-finite element in it, or in every centroid; a NaN distance counts as +inf) gets
+ *   label -1 and d2 = +inf; a non-finite centroid is nobody's label.  *inertia = the sum of d2 over the rows that have a
+ *   label, in f64, added in a fixed tree.  K < 2^32 - 1; X, C as for am_knn_search_f32 (16-byte aligned, ld % 4 == 0,
+ *   ld >= D).  Workspace: the row norms, uint64 [column chunks][N] keys and one f64 per 256 rows.
+ *
+ *   UPDATE.  C_new[c] = the mean of the rows with label c: summed in f64 in the order of `order`, divided in f64, rounded
+ *   to f32 once; counts[c] = their number.  A cluster without rows copies C_old[c] bit for bit and reports 0.
+ *   order   int64 [N]      the row indices sorted by label, stable (rows of one cluster in ascending row order)
+ *   offsets int64 [K + 1]  cluster c is order[offsets[c] .. offsets[c + 1]); rows with label -1 come FIRST, in
+ *                          order[0 .. offsets[0]), and are not read
+ *   labels  int64 [N]      the labels `order` and `offsets` were built from (the kernel looks the cluster of a position
+ *                          up as labels[order[p]]); a label outside 0 .. K - 1 is skipped
+ *   `order` is cut into segments of 64 positions; a cluster that crosses segments is summed per segment and the partial
+ *   sums are added in segment order.  Every index taken from the three arrays is range-checked before it addresses
+ *   memory.  C_new may be C_old.  Workspace: f64 [ceil(N / 64)][2][D rounded up to 4].
+ * ------------------------------------------------------------------------- */
+size_t am_kmeans_assign_workspace_bytes(int64_t N, int64_t K, int D);
+int am_kmeans_assign_f32(const float* X, int64_t N, int64_t ldx, const float* C, int64_t K, int64_t ldc, int D,
+                         int64_t* labels, float* d2, double* inertia,
+                         void* ws, size_t ws_bytes, am_stream_t stream);
+size_t am_kmeans_update_workspace_bytes(int64_t N, int64_t K, int D);
+int am_kmeans_update_f32(const float* X, int64_t N, int64_t ldx, int D,
+                         const int64_t* labels, const int64_t* order, const int64_t* offsets, int64_t K,
+                         const float* C_old, int64_t ldc_old, float* C_new, int64_t ldc_new, int64_t* counts,
+                         void* ws, size_t ws_bytes, am_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * A9, partitioned form for one-process-per-GPU callers that all hold the FULL set X.
  * The self-distance matrix is bitwise symmetric, so only half of the tile pairs are multiplied
  * (csrc/pairwise.hip, knn_sym_kernel); rank `part` of `nparts` owns a contiguous range of the 128-row blocks.
