@@ -13,6 +13,7 @@ from .metrics.fad import frechet_distance_per_group                           # 
 from .metrics.kd import kernel_distance, kid_features_to_metric               # noqa: F401
 from .metrics.kad import kernel_audio_distance                                # noqa: F401
 from .metrics.kad import kernel_audio_distance_per_group                      # noqa: F401
+from .metrics.mmd import kernel_audio_distance_multiscale, energy_distance   # noqa: F401
 from .metrics.prdc import prdc, nearest_neighbour_distances                   # noqa: F401
 from .metrics.neighbors import nearest_neighbors                              # noqa: F401
 from .metrics.mauve import kmeans, mauve_score, mauve_from_histograms         # noqa: F401

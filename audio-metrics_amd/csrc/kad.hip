@@ -333,13 +333,8 @@ __global__ void __launch_bounds__(256) kad_reduce_kernel(const double* __restric
     if (tid == 0) out[0] = red[0];
 }
 
-struct MmdPlan {
-    int chunk[3];
-    dim3 grid[3];
-    size_t slots[3];
-};
-
-static MmdPlan mmd_plan(int64_t N1, int64_t N2) {
+// the grids of the three blocks (kad_common.h)
+MmdPlan mmd_plan(int64_t N1, int64_t N2) {
     MmdPlan p;
     const int64_t T1 = ceil_div(N1, TB), T2 = ceil_div(N2, TB);
     const int64_t tq[3] = {T1, T2, T1}, tp[3] = {T1, T2, T2};

@@ -731,6 +731,86 @@ def mmd_rbf_sums(x, y, bw2=None, gamma=None, blocks=7, out=None):
     return out
 
 
+MMD_KERNELS = {"gaussian": 0, "laplacian": 1, "energy": 2}        # enum am_mmd_kernel
+MMD_MULTI_MAX = 4                                                    # AM_MMD_MULTI_MAX: scales per library call
+
+
+def mmd_scales(scales):
+    """The scale grid as a list of finite positive floats (at least one), or ValueError."""
+    try:
+        grid = [float(c) for c in scales]
+    except TypeError:
+        raise ValueError(f"scales must be a sequence of numbers, got {scales!r}") from None
+    if not grid:
+        raise ValueError("scales is empty: at least one scale is needed")
+    for c in grid:
+        if not (c > 0.0 and c < float("inf")):
+            raise ValueError(f"scales must be finite and positive, got {c!r}")
+    return grid
+
+
+def mmd_multi_sums(x, y, kernel, scales, bw2=None, blocks=7, out=None):
+    """float64 [3, S] device tensor: row 0 Sxx, 1 Syy, 2 Sxy (ordered pairs i != j / all pairs, as mmd_rbf_sums) of S kernels
+    of one family in one Gram pass per at most four scales (am_mmd_multi_f32).  `kernel`: "gaussian" exp(-d2 g),
+    g = 0.5 / (bw2 c c); "laplacian" exp(-d h), h = 1 / (c sqrt(bw2)); "energy" -d (one scale, no bandwidth) - c running over
+    `scales`.  `bw2`: a 0-dim float32 DEVICE tensor (the output of pairwise_select_sq, no host round trip) or a number.  The
+    Gaussian column of scale c holds the bits of mmd_rbf_sums(gamma=0.5 / (bw2 * (c * c))); no column depends on the other
+    scales or on where a longer grid is cut into calls.  Only the rows named by `blocks` are written; the others keep what
+    `out` held (NaN in a fresh tensor).  float32 rows only; stream-ordered, nothing waits for the device."""
+    if kernel not in MMD_KERNELS:
+        raise ValueError(f"kernel={kernel!r} is not one of {sorted(MMD_KERNELS)}")
+    grid = mmd_scales(scales)
+    if kernel == "energy" and len(grid) != 1:
+        raise ValueError(f'the "energy" kernel has no bandwidth: it takes one scale, got {len(grid)}')
+    for t, name in ((x, "x"), (y, "y")):
+        if is_f64(t):
+            raise NotImplementedError(f"mmd_multi_sums takes float32 rows ({name} holds float64 rows; the float64 matrix-core form "
+                                      "is not implemented)")
+        if not torch.is_tensor(t) or t.dim() != 2:
+            raise ValueError(f"{name} must be a 2-D tensor, got {tuple(getattr(t, 'shape', ()))}")
+    if x.shape[1] != y.shape[1]:
+        raise ValueError(f"feature widths differ: {x.shape[1]} and {y.shape[1]}")
+    blocks = int(blocks)
+    if blocks < 1 or blocks > 7:
+        raise ValueError(f"blocks={blocks} is not a mask of MMD_XX | MMD_YY | MMD_XY")
+    bw2_arg, bw2_host = ctypes.c_void_p(None), 0.0
+    if kernel != "energy":
+        if bw2 is None:
+            raise ValueError(f'the "{kernel}" kernel needs bw2 (a float32 device scalar or a number)')
+        if torch.is_tensor(bw2):
+            _require_cuda(bw2, "bw2")
+            if bw2.dtype != torch.float32 or bw2.numel() != 1:
+                raise ValueError("bw2 must be a float32 device scalar")
+            bw2_arg = _ptr(bw2)
+        else:
+            bw2_host = float(bw2)
+            if not (bw2_host > 0.0 and bw2_host < float("inf")):
+                raise ValueError(f"bw2={bw2!r} must be finite and positive")
+    nscales = len(grid)
+    lib = _lib.load()
+    x, y = as_matrix(x, "x"), as_matrix(y, "y")
+    dev = _same_device(x, y)
+    if out is None:
+        out = torch.full((3, nscales), float("nan"), dtype=torch.float64, device=dev)
+    elif not (out.device == dev and out.dtype == torch.float64 and tuple(out.shape) == (3, nscales) and out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous float64 [3, {nscales}] tensor on the device of the rows")
+    (n, d), m = x.shape, y.shape[0]
+    rows = [b for b in range(3) if blocks & (1 << b)]
+    for first in range(0, nscales, MMD_MULTI_MAX):
+        part = grid[first:first + MMD_MULTI_MAX]
+        k = len(part)
+        # the library writes a dense [3][k]: the whole of `out`, or a staging tensor whose named rows go to columns first .. first + k
+        dst = out if k == nscales else torch.empty((3, k), dtype=torch.float64, device=dev)
+        nb = lib.am_mmd_multi_workspace_bytes(n, m, d, k, blocks)
+        ws = _workspace(nb, dev)
+        _call(lib, "am_mmd_multi_f32", dev, _ptr(x), n, _ld(x), _ptr(y), m, _ld(y), d, MMD_KERNELS[kernel], bw2_arg, bw2_host,
+              ctypes.cast((ctypes.c_double * k)(*part), ctypes.c_void_p), k, blocks, _ptr(dst), _ptr(ws), nb)
+        if dst is not out:
+            for b in rows:
+                out[b, first:first + k].copy_(dst[b])
+    return out
+
+
 def mmd_rbf_group_sums(x, idx, offsets, y, bw2=None, gamma=None, rows=False):
     """Per-group Gaussian kernel sums in one library call (am_mmd_rbf_groups_f32; both sets float64:
     am_mmd_rbf_groups_f64): group b is the rows

@@ -290,6 +290,37 @@ int am_mmd_rbf_f32(const float* X, int64_t N1, int64_t ldx,
                    double* out_sums, void* ws, size_t ws_bytes, am_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Whole-set kernel sums under several kernels at once (csrc/mmd_multi.hip, f32 tile engine): the three sums of
+ * am_mmd_rbf_f32 for up to AM_MMD_MULTI_MAX scales of one kernel family in ONE Gram pass - the tile work of a block is done
+ * once and every scale is one more epilogue value on the same accumulator tile.  With d2 as above and the scales c_s:
+ *   AM_MMD_GAUSSIAN   k = exp(-d2 g_s),        g_s = 0.5 / (bw2 * (c_s * c_s))
+ *   AM_MMD_LAPLACIAN  k = exp(-sqrt(d2) h_s),  h_s = 1.0 / (c_s * sqrt(bw2))
+ *   AM_MMD_ENERGY     k = -sqrt(d2)            nscales must be 1; bw2_dev, bw2 and the scale's value are ignored (the MMD^2
+ *                                              of this kernel is the energy distance 2 E|x - y| - E|x - x'| - E|y - y'|)
+ * the parameters formed in f64 in exactly that order.  bw2 = (double)*bw2_dev when bw2_dev != NULL (DEVICE float: the output
+ * of the select feeds the call with no host round trip), else the `bw2` argument.
+ *   out_sums  DEVICE [3][nscales] doubles: out_sums[b * nscales + s], b = 0 Sxx, 1 Syy, 2 Sxy (ordered pairs i != j / all
+ *             pairs, as for am_mmd_rbf_f32); only the blocks named by `blocks` are written
+ *   scales    HOST, nscales entries, each finite and > 0
+ * Grid plan, upper-triangular sweep, f64 norms and summation order are those of am_mmd_rbf_f32, one running sum per scale:
+ * the Gaussian sums of scale c equal those of am_mmd_rbf_f32 with gamma = 0.5 / (bw2 * (c * c)) bit for bit, a scale's sums
+ * depend neither on the other scales of the call nor on their order, and two calls give the same bits (one f64 partial per
+ * workgroup and scale, summed in a fixed order; no floating-point atomics).  A non-finite row makes the sums it takes part
+ * in NaN.  X, Y, N1, N2, D, blocks, the 4 GiB rule: as for am_mmd_rbf_f32.  nscales outside 1 .. AM_MMD_MULTI_MAX (the
+ * register file holds four scales without scratch memory; a longer grid is several calls) -> AM_ERR_BAD_SHAPE; an unknown
+ * kernel, a scale that is not finite and positive, or bw2_dev == NULL with bw2 not finite and positive (except for the
+ * energy kernel) -> AM_ERR_BAD_ARG.  Validated before the first HIP call; stream-ordered, no host synchronisation.
+ * ------------------------------------------------------------------------- */
+enum am_mmd_kernel { AM_MMD_GAUSSIAN = 0, AM_MMD_LAPLACIAN = 1, AM_MMD_ENERGY = 2 };
+#define AM_MMD_MULTI_MAX 4
+size_t am_mmd_multi_workspace_bytes(int64_t N1, int64_t N2, int D, int nscales, unsigned blocks);
+int am_mmd_multi_f32(const float* X, int64_t N1, int64_t ldx,
+                     const float* Y, int64_t N2, int64_t ldy, int D,
+                     int kernel, const float* bw2_dev, double bw2,
+                     const double* scales, int nscales, unsigned blocks,
+                     double* out_sums, void* ws, size_t ws_bytes, am_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Per-group Kernel Audio Distance (csrc/kad_groups.hip, f32 tile engine): the Gaussian kernel sums of B groups of rows of
  * one stored matrix X, each group on its own against the one reference set Y, in ONE call whose number of launches does not
  * depend on B.  Group b is the rows X[idx[offsets[b] + j]], j < n_b; idx == NULL names the rows in stored order.  With
