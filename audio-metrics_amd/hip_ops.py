@@ -731,6 +731,40 @@ def mmd_rbf_sums(x, y, bw2=None, gamma=None, blocks=7, out=None):
     return out
 
 
+def mmd_rbf_row_sums(x, y, bw2=None, gamma=None, blocks=7):
+    """Two-sided row sums of the Gaussian kernel blocks in one library call (am_mmd_rbf_rows_f32): (out_x, out_y), float64
+    device tensors [n, 2] = {w_i, c_i} and [m, 2] = {v_j, r_j} with w_i = sum_{j != i} k(x_i, x_j) (MMD_XX), v_j the same
+    inside y (MMD_YY), c_i = sum_j k(x_i, y_j) and r_j = sum_i k(x_i, y_j) (MMD_XY) - every Gram tile computed once, the
+    work of mmd_rbf_sums with the same `blocks`.  A side no named block writes is None; a column of a block that is not
+    named holds NaN.  `bw2` / `gamma` as for mmd_rbf_sums.  float32 rows only; stream-ordered, nothing waits for the
+    device."""
+    for t, name in ((x, "x"), (y, "y")):
+        if is_f64(t):
+            raise NotImplementedError(f"mmd_rbf_row_sums takes float32 rows ({name} holds float64 rows; the float64 matrix-core "
+                                      "form is not implemented)")
+        if not torch.is_tensor(t) or t.dim() != 2:
+            raise ValueError(f"{name} must be a 2-D tensor, got {tuple(getattr(t, 'shape', ()))}")
+    if x.shape[1] != y.shape[1]:
+        raise ValueError(f"feature widths differ: {x.shape[1]} and {y.shape[1]}")
+    blocks = int(blocks)
+    if blocks < 1 or blocks > 7:
+        raise ValueError(f"blocks={blocks} is not a mask of MMD_XX | MMD_YY | MMD_XY")
+    bw2_arg, gamma_arg = _bandwidth_args(bw2, gamma)
+    lib = _lib.load()
+    x, y = as_matrix(x, "x"), as_matrix(y, "y")
+    dev = _same_device(x, y)
+    (n, d), m = x.shape, y.shape[0]
+    nan = float("nan")
+    out_x = torch.full((n, 2), nan, dtype=torch.float64, device=dev) if blocks & (MMD_XX | MMD_XY) else None
+    out_y = torch.full((m, 2), nan, dtype=torch.float64, device=dev) if blocks & (MMD_YY | MMD_XY) else None
+    nb = lib.am_mmd_rbf_rows_workspace_bytes(n, m, d, blocks)
+    ws = _workspace(nb, dev)
+    null = ctypes.c_void_p(None)
+    _call(lib, "am_mmd_rbf_rows_f32", dev, _ptr(x), n, _ld(x), _ptr(y), m, _ld(y), d, bw2_arg, gamma_arg, blocks,
+          _ptr(out_x) if out_x is not None else null, _ptr(out_y) if out_y is not None else null, _ptr(ws), nb)
+    return out_x, out_y
+
+
 MMD_KERNELS = {"gaussian": 0, "laplacian": 1, "energy": 2}        # enum am_mmd_kernel
 MMD_MULTI_MAX = 4                                                    # AM_MMD_MULTI_MAX: scales per library call
 

@@ -39,6 +39,7 @@ class _ReferenceCache:
         self.bw2 = None            # 0-dim float32 device tensor: median squared distance
         self.bw2_host = None       # its value, once a result has been read back
         self.syy = {}              # gamma bits -> 0-dim float64 device tensor
+        self.vrow = {}             # gamma bits -> float64 [m] device tensor: the row sums v_j of Kyy (metrics/kad_stats.py)
 
 
 def reference_cache(y):

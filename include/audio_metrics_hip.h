@@ -290,6 +290,35 @@ int am_mmd_rbf_f32(const float* X, int64_t N1, int64_t ldx,
                    double* out_sums, void* ws, size_t ws_bytes, am_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Two-sided row sums of the three Gaussian kernel blocks (csrc/mmd_rows.hip, f32 tile engine): what the closed-form
+ * standard error of the unbiased MMD^2 and the two-model comparison are built from, for the Gram and exp work of
+ * am_mmd_rbf_f32.  With k = exp(-d2 gamma), d2 and gamma / bw2_dev as for am_mmd_rbf_f32:
+ *   out_x  DEVICE [N1][2] doubles {w_i, c_i}:  w_i = sum_{j != i} k(x_i, x_j) (AM_MMD_XX),  c_i = sum_j k(x_i, y_j) (AM_MMD_XY)
+ *   out_y  DEVICE [N2][2] doubles {v_j, r_j}:  v_j = sum_{l != j} k(y_j, y_l) (AM_MMD_YY),  r_j = sum_i k(x_i, y_j) (AM_MMD_XY)
+ * `blocks` is a mask of AM_MMD_XX | AM_MMD_YY | AM_MMD_XY; the slots of blocks it does not name are not written, and out_x
+ * (out_y) may be NULL when neither AM_MMD_XX (AM_MMD_YY) nor AM_MMD_XY is named.  sum w = Sxx, sum v = Syy, sum c = sum r =
+ * Sxy of am_mmd_rbf_f32 up to the summation order.  Self pairs are excluded by INDEX: duplicated rows stay each other's
+ * pairs with k = 1; a set of one row has w (v) = 0.
+ * Every 128 x 128 tile is computed ONCE and summed along both axes of the accumulator: XX and YY sweep the upper-triangular
+ * tiles (an off-diagonal tile feeds the sums of its P rows and of its Q rows, the diagonal tile its P rows only), XY every
+ * tile once (P = X, Q = Y).  The P tiles are swept in bands of 64; after each band the band's Q-side partials are added to
+ * running f64 sums in P-tile order, so the workspace holds 1 KiB per row of the larger set whatever the other's size
+ * (100 000 x 100 000 rows: about 105 MiB).  No floating-point atomics: two calls give the same bits, and a block's outputs
+ * do not depend on which other blocks share the call.  A non-finite row makes every sum it takes part in NaN - its own,
+ * every w of its set and every cross sum of the other set - and no other.
+ * X, Y, N1 != N2, ld, alignment, any D >= 1, the 4 GiB rule: as for am_mmd_rbf_f32.  A null X / Y or a null output of a named
+ * block, a bad mask, alignment or ld, gamma < 0 without bw2_dev -> AM_ERR_BAD_ARG; N1, N2 or D < 1, a set of 4 GiB ->
+ * AM_ERR_BAD_SHAPE; AM_ERR_WORKSPACE.  Validated before the first HIP call; stream-ordered, no host synchronisation.
+ * ------------------------------------------------------------------------- */
+size_t am_mmd_rbf_rows_workspace_bytes(int64_t N1, int64_t N2, int D, unsigned blocks);
+int am_mmd_rbf_rows_f32(const float* X, int64_t N1, int64_t ldx,
+                        const float* Y, int64_t N2, int64_t ldy, int D,
+                        const float* bw2_dev, double gamma, unsigned blocks,
+                        double* out_x,   /* DEVICE [N1][2] = {w_i, c_i} */
+                        double* out_y,   /* DEVICE [N2][2] = {v_j, r_j} */
+                        void* ws, size_t ws_bytes, am_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Whole-set kernel sums under several kernels at once (csrc/mmd_multi.hip, f32 tile engine): the three sums of
  * am_mmd_rbf_f32 for up to AM_MMD_MULTI_MAX scales of one kernel family in ONE Gram pass - the tile work of a block is done
  * once and every scale is one more epilogue value on the same accumulator tile.  With d2 as above and the scales c_s:
