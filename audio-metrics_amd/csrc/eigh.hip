@@ -15,6 +15,12 @@
 // spread over 8 workgroups per pair).  The rounds of several sweeps are enqueued ahead: a kernel of sweep s returns at once
 // when sweep s - 1 applied no rotation (counter on the device), so the host synchronises once per block of sweeps -
 // normally once per solve - instead of once per sweep.  All reductions run in a fixed order (deterministic).
+// Scale: the rotation test compares squared row norms of W, quantities of order lambda^4, which leave the f64 range for
+// eigenvalues beyond 2^+-256.  A is therefore brought to unit scale first: W starts as 2^-e A with 2^e <= trace A < 2^(e+1)
+// (a power of two: exact, and every later operation commutes with it, so the result has the bits of the unscaled solve
+// wherever that one stayed in range), and the eigenvalues are multiplied by 2^e at the end.
+// Non-finite input: gate[0] is cleared by the kernels that read A; every kernel of every sweep then returns at once and the
+// host reports AM_ERR_NO_CONVERGENCE without touching evals / evecs.
 #include "am_common.h"
 #include <math.h>
 #include <stdlib.h>
@@ -47,8 +53,25 @@ __device__ __forceinline__ double block_sum3(double& a, double& b, double& c, do
 // rank[i] = position of row i when the rows of A are ordered by decreasing diagonal entry (ties by index).  One-sided
 // Jacobi converges in fewer sweeps when rows of similar norm sit together and the larger ones come first (de Rijk's
 // ordering); for the Gram matrices of a PCA fit the diagonal is a good proxy of the final row norms.
-__global__ void __launch_bounds__(256) jacobi_rank_kernel(const double* __restrict__ A, int n, int* __restrict__ rank) {
+// Thread 0 also takes the trace, BEFORE any row of W is formed (jacobi_init_kernel is the next launch and scales by it):
+//   scale[0] = 2^-e trace A in [1, 2)   (>= the largest eigenvalue of the scaled matrix: A is positive semi-definite)
+//   scale[1] = 2^-e, scale[2] = 2^e     (e clamped to [-1022, 1023] so that both are normal numbers; trace A == 0: e = 0)
+// and opens the gate of sweep 0 when the trace is finite.
+__global__ void __launch_bounds__(256) jacobi_rank_kernel(const double* __restrict__ A, int n, int* __restrict__ rank,
+                                                          double* __restrict__ scale, unsigned* __restrict__ gate) {
     const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i == 0) {                                      // fixed order
+        double t = 0.0;
+        for (int j = 0; j < n; ++j) t += fabs(A[(int64_t)j * n + j]);
+        const bool finite = t <= 1.7976931348623157e308;          // false for NaN and +inf
+        int e = (finite && t > 0.0) ? ilogb(t) : 0;
+        e = max(-1022, min(1023, e));
+        const double down = ldexp(1.0, -e);
+        scale[0] = finite ? t * down : 0.0;
+        scale[1] = down;
+        scale[2] = ldexp(1.0, e);
+        gate[0] = finite ? 1u : 0u;
+    }
     if (i >= n) return;
     const double di = fabs(A[(int64_t)i * n + i]);
     int before = 0;
@@ -59,21 +82,23 @@ __global__ void __launch_bounds__(256) jacobi_rank_kernel(const double* __restri
     rank[i] = before;
 }
 
-// W = P A, V = P (row rank[i] of W is row i of A)
+// W = 2^-e P A, V = P (row rank[i] of W is row i of A).  Every entry of A passes through here: a NaN or an infinity closes the
+// gate of sweep 0 (all writers store the same value).
 __global__ void __launch_bounds__(256) jacobi_init_kernel(const double* __restrict__ A, int n, const int* __restrict__ rank,
-                                                          double* __restrict__ W, double* __restrict__ V, double* __restrict__ scale) {
+                                                          double* __restrict__ W, double* __restrict__ V,
+                                                          const double* __restrict__ scale, unsigned* __restrict__ gate) {
     const int64_t total = (int64_t)n * n;
+    const double down = scale[1];
+    bool bad = false;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int row = (int)(i / n), col = (int)(i % n);
         const int64_t o = (int64_t)rank[row] * n + col;
-        W[o] = A[i];
+        const double a = A[i];
+        bad = bad || !(fabs(a) <= 1.7976931348623157e308);
+        W[o] = a * down;
         V[o] = row == col ? 1.0 : 0.0;
     }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {        // trace A >= largest eigenvalue (A is positive semi-definite), fixed order
-        double t = 0.0;
-        for (int i = 0; i < n; ++i) t += fabs(A[(int64_t)i * n + i]);
-        *scale = t;
-    }
+    if (bad) gate[0] = 0u;
 }
 
 // 1 / sqrt(y) and 1 / y for positive normal y: hardware estimate + two Newton steps (quadratic: 2^-26 -> 2^-52)
@@ -125,12 +150,13 @@ struct BlockPair {
 //   1. jacobi_gram_kernel   partial Gram matrices of the pair's 32 rows of W, one per column slice      (pairs x 8 workgroups)
 //   2. jacobi_inner_kernel  G = sum of the partials; two-sided Jacobi of G in LDS, rotations accumulated in J      (pairs)
 //   3. jacobi_apply_kernel  rows <- J^T rows for W and V, the 16-column strips dealt over the workgroups  (pairs x 8 workgroups)
-// Every kernel of sweep s returns at once when sweep s - 1 applied no rotation.
+// Every kernel of sweep s returns at once when gate[s] == 0: gate[0] = the input is finite, gate[s + 1] = block pairs that
+// rotated in sweep s.
 
 // ---- 1. Gpart[pair][slice] = R[:, slice] R[:, slice]^T on v_mfma_f64_16x16x4_f64: wave w owns the 16 x 16 tile (w >> 1, w & 1)
 __global__ void __launch_bounds__(256) jacobi_gram_kernel(const double* __restrict__ W, int n, int nb, int mb, int round, int sweep,
-                                                          const unsigned* __restrict__ rotations, double* __restrict__ Gpart) {
-    if (sweep > 0 && rotations[sweep - 1] == 0u) return;           // the previous sweep found every pair orthogonal: done
+                                                          const unsigned* __restrict__ gate, double* __restrict__ Gpart) {
+    if (gate[sweep] == 0u) return;                                 // the previous sweep found every pair orthogonal: done
     const BlockPair bpair(blockIdx.x, mb, round, n, nb);
     if (bpair.bye()) return;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -185,13 +211,14 @@ __global__ void __launch_bounds__(256) jacobi_gram_kernel(const double* __restri
 // ONE inner sweep per visit: the pair's rows meet again in the next outer sweep, and a full diagonalisation of G here (5-8 inner
 // sweeps while the off-diagonal mass is large) costs more than the outer sweeps it saves - measured 54 ms against 28.
 __global__ void __launch_bounds__(256) jacobi_inner_kernel(const double* __restrict__ Gpart, int n, int nb, int mb, int round, int sweep,
-                                                           double tol, const double* __restrict__ scale, unsigned* __restrict__ rotations,
+                                                           double tol, const double* __restrict__ scale, unsigned* __restrict__ gate,
                                                            double* __restrict__ Jout, int* __restrict__ applied_out) {
-    if (sweep > 0 && rotations[sweep - 1] == 0u) return;
+    if (gate[sweep] == 0u) return;
     const BlockPair bpair(blockIdx.x, mb, round, n, nb);
     if (bpair.bye()) return;
-    // rows whose squared norm is below (1e-14 trace A)^2 are numerically zero (null directions of a rank-deficient A: their
-    // content is rounding noise, whose mutual angles never settle - 3x the sweeps on a Gram matrix of D/3 rows)
+    // rows whose squared norm is below (1e-14 trace)^2 - of the scaled matrix, as W is - are numerically zero (null directions of
+    // a rank-deficient A: their content is rounding noise, whose mutual angles never settle - 3x the sweeps on a Gram matrix
+    // of D/3 rows)
     const double floor2 = (1e-14 * *scale) * (1e-14 * *scale), tol2 = tol * tol;
     __shared__ double G[2][JP][JLD], J[2][JP][JLD];
     __shared__ int applied;
@@ -277,7 +304,7 @@ __global__ void __launch_bounds__(256) jacobi_inner_kernel(const double* __restr
     const bool any = applied != 0;
     if (tid == 0) {
         applied_out[blockIdx.x] = any ? 1 : 0;
-        if (any) atomicAdd(rotations + sweep, 1u);
+        if (any) atomicAdd(gate + sweep + 1, 1u);
     }
     if (!any) return;                                                // the 32 rows were orthogonal already: nothing to apply
     double* jo = Jout + (int64_t)blockIdx.x * (JP * JP);
@@ -288,9 +315,9 @@ __global__ void __launch_bounds__(256) jacobi_inner_kernel(const double* __restr
 //         loads the strips' 32 x 16 blocks (eight k-steps of four rows), forms both 16-row output tiles of each, stores them
 //         back (16 loads in flight and four independent MFMA chains; 128 workgroups per round at D = 512).
 __global__ void __launch_bounds__(256) jacobi_apply_kernel(double* __restrict__ W, double* __restrict__ V, int n, int nb, int mb,
-                                                           int round, int sweep, const unsigned* __restrict__ rotations,
+                                                           int round, int sweep, const unsigned* __restrict__ gate,
                                                            const double* __restrict__ Jin, const int* __restrict__ applied_in) {
-    if (sweep > 0 && rotations[sweep - 1] == 0u) return;
+    if (gate[sweep] == 0u) return;
     const BlockPair bpair(blockIdx.x, mb, round, n, nb);
     if (bpair.bye() || applied_in[blockIdx.x] == 0) return;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -346,15 +373,15 @@ __global__ void __launch_bounds__(256) jacobi_apply_kernel(double* __restrict__ 
     }
 }
 
-// lambda_i = W_i . V_i
+// lambda_i = 2^e W_i . V_i
 __global__ void __launch_bounds__(256) jacobi_values_kernel(const double* __restrict__ W, const double* __restrict__ V, int n,
-                                                            double* __restrict__ lambda) {
+                                                            const double* __restrict__ scale, double* __restrict__ lambda) {
     __shared__ double red[4][3];
     const int i = blockIdx.x;
     double a = 0, b = 0, c = 0;
     for (int k = threadIdx.x; k < n; k += 256) a = fma(W[(int64_t)i * n + k], V[(int64_t)i * n + k], a);
     block_sum3(a, b, c, red);
-    if (threadIdx.x == 0) lambda[i] = a;
+    if (threadIdx.x == 0) lambda[i] = a * scale[2];
 }
 
 // descending order: position of eigenpair i = number of pairs that come before it (ties by index)
@@ -419,8 +446,8 @@ extern "C" size_t am_eigh_workspace_bytes(int D) {
     c.take<double>((size_t)D * D);     // W
     c.take<double>((size_t)D * D);     // V
     c.take<double>((size_t)D);         // lambda (unsorted)
-    c.take<unsigned>(64);              // rotation counters, one per sweep
-    c.take<double>(1);                 // trace of A
+    c.take<unsigned>(65);              // gate[0] = input finite, gate[s + 1] = rotation counter of sweep s
+    c.take<double>(3);                 // scaled trace of A, 2^-e, 2^e
     c.take<int>(D);                    // initial row order
     const size_t pairs = (size_t)((D + JB - 1) / JB + 1) / 2;
     c.take<double>(pairs * GRAM_SLICES * JP * JP);   // partial Gram matrices of a round
@@ -439,50 +466,51 @@ extern "C" int am_eigh_sym_f64(const double* A, int D, double* evals, double* ev
     double* W = c.take<double>((size_t)D * D);
     double* V = c.take<double>((size_t)D * D);
     double* lambda = c.take<double>((size_t)D);
-    unsigned* rotations = c.take<unsigned>(64);
-    double* scale = c.take<double>(1);
+    unsigned* gate = c.take<unsigned>(65);
+    double* scale = c.take<double>(3);
     int* rank = c.take<int>(D);
     const size_t pairs = (size_t)((D + JB - 1) / JB + 1) / 2;
     double* Gpart = c.take<double>(pairs * GRAM_SLICES * JP * JP);
     double* Jbuf = c.take<double>(pairs * JP * JP);
     int* applied = c.take<int>(pairs);
     AM_REQUIRE(c.ok(), AM_ERR_WORKSPACE, "workspace too small: need %zu bytes, have %zu", c.off, ws_bytes);
-    hipLaunchKernelGGL(jacobi_rank_kernel, dim3((unsigned)ceil_div(D, 256)), dim3(256), 0, st, A, D, rank);
+    AM_HIP_TRY(hipMemsetAsync(gate, 0, 65 * sizeof(unsigned), st));
+    hipLaunchKernelGGL(jacobi_rank_kernel, dim3((unsigned)ceil_div(D, 256)), dim3(256), 0, st, A, D, rank, scale, gate);
     hipLaunchKernelGGL(jacobi_init_kernel, dim3((unsigned)std::min<int64_t>(1024, ceil_div((int64_t)D * D, 256))), dim3(256), 0, st, A, D,
-                       rank, W, V, scale);
+                       rank, W, V, scale, gate);
     AM_LAUNCH_CHECK();
-    AM_HIP_TRY(hipMemsetAsync(rotations, 0, 64 * sizeof(unsigned), st));
     const int nb = (D + JB - 1) / JB, mb = (nb + 1) / 2 * 2;
     const double tol = 1e-14 * sqrt((double)D);       // |W_p . W_q| <= tol |W_p| |W_q|: the rounding level of a D-term f64 dot product
     // Sweeps are enqueued in blocks; a round kernel returns at once when the sweep before it applied no rotation, so
     // running ahead costs only empty launches.  One read-back per block: normally one per solve.
     bool converged = false;
-    unsigned counts[64];
+    unsigned counts[65];
     for (int done = 0; done < max_sweeps && !converged;) {
         const int block = std::min(done == 0 ? 12 : 6, max_sweeps - done);
         for (int sweep = done; sweep < done + block; ++sweep)
             for (int round = 0; round < mb - 1; ++round) {
-                hipLaunchKernelGGL(jacobi_gram_kernel, dim3(mb / 2, GRAM_SLICES), dim3(256), 0, st, W, D, nb, mb, round, sweep, rotations, Gpart);
-                hipLaunchKernelGGL(jacobi_inner_kernel, dim3(mb / 2), dim3(256), 0, st, Gpart, D, nb, mb, round, sweep, tol, scale, rotations,
+                hipLaunchKernelGGL(jacobi_gram_kernel, dim3(mb / 2, GRAM_SLICES), dim3(256), 0, st, W, D, nb, mb, round, sweep, gate, Gpart);
+                hipLaunchKernelGGL(jacobi_inner_kernel, dim3(mb / 2), dim3(256), 0, st, Gpart, D, nb, mb, round, sweep, tol, scale, gate,
                                    Jbuf, applied);
-                hipLaunchKernelGGL(jacobi_apply_kernel, dim3(mb / 2, APPLY_SLICES), dim3(256), 0, st, W, V, D, nb, mb, round, sweep, rotations,
+                hipLaunchKernelGGL(jacobi_apply_kernel, dim3(mb / 2, APPLY_SLICES), dim3(256), 0, st, W, V, D, nb, mb, round, sweep, gate,
                                    Jbuf, applied);
             }
         AM_LAUNCH_CHECK();
         done += block;
-        AM_HIP_TRY(hipMemcpyAsync(counts, rotations, (size_t)done * sizeof(unsigned), hipMemcpyDeviceToHost, st));
+        AM_HIP_TRY(hipMemcpyAsync(counts, gate, (size_t)(done + 1) * sizeof(unsigned), hipMemcpyDeviceToHost, st));
         AM_HIP_TRY(hipStreamSynchronize(st));
-        for (int sweep = 0; sweep < done; ++sweep) converged = converged || counts[sweep] == 0u;
+        AM_REQUIRE(counts[0] != 0u, AM_ERR_NO_CONVERGENCE, "Jacobi eigensolver: non-finite entry in A, or a trace that overflows");
+        for (int sweep = 0; sweep < done; ++sweep) converged = converged || counts[sweep + 1] == 0u;
 #ifdef AM_DEV_KNOBS
         if (getenv("AM_EIGH_DEBUG")) {                 // block pairs that rotated, per sweep (development aid)
             fprintf(stderr, "[am eigh] D=%d sweeps enqueued %d:", D, done);
-            for (int sweep = 0; sweep < done; ++sweep) fprintf(stderr, " %u", counts[sweep]);
+            for (int sweep = 0; sweep < done; ++sweep) fprintf(stderr, " %u", counts[sweep + 1]);
             fprintf(stderr, "\n");
         }
 #endif
     }
     AM_REQUIRE(converged, AM_ERR_NO_CONVERGENCE, "Jacobi eigensolver: rows still not orthogonal after %d sweeps", max_sweeps);
-    hipLaunchKernelGGL(jacobi_values_kernel, dim3(D), dim3(256), 0, st, W, V, D, lambda);
+    hipLaunchKernelGGL(jacobi_values_kernel, dim3(D), dim3(256), 0, st, W, V, D, scale, lambda);
     hipLaunchKernelGGL(jacobi_sort_kernel, dim3(D), dim3(256), 0, st, lambda, V, D, evals, evecs);
     AM_LAUNCH_CHECK();
     return AM_OK;

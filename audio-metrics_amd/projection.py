@@ -53,7 +53,7 @@ class IncrementalPCA:
             n_samples = int(batch_stats[0])
         first_pass = getattr(self, "components_", None) is None
         if self.n_components is None:
-            self.n_components_ = min(n_samples, n_features) if first_pass else self.components_.shape[0]
+            p = min(n_samples, n_features) if first_pass else self.components_.shape[0]
         elif not self.n_components <= n_features:
             raise ValueError("n_components=%r invalid for n_features=%d, need more rows than columns for "
                              "IncrementalPCA processing" % (self.n_components, n_features))
@@ -61,7 +61,7 @@ class IncrementalPCA:
             raise ValueError(f"n_components={self.n_components} must be less or equal to the batch number of samples "
                              f"{n_samples} for the first partial_fit call.")
         else:
-            self.n_components_ = self.n_components
+            p = self.n_components
 
         if batch_stats is not None:
             mean_b, cov_b = (ensure_tensor(t).to(X.device, torch.float64) for t in batch_stats[1:])
@@ -91,7 +91,9 @@ class IncrementalPCA:
             gram = (c.T * s2) @ c + scatter_b + torch.outer(corr, corr)
             rows = c.shape[0] + n_samples + 1
         gram = 0.5 * (gram + gram.T)
-        evals, vt = ops.eigh_descending(gram)                 # descending; rows of vt = right singular vectors
+        # descending; rows of vt = right singular vectors.  A non-finite batch raises here (am_eigh_sym_f64 refuses a non-finite
+        # matrix), before any fitted attribute has been touched
+        evals, vt = ops.eigh_descending(gram)
         evals = evals.clamp_min(0.0)
         # svd_flip(u_based_decision=False): the entry of largest magnitude in each row becomes positive
         idx = vt.abs().argmax(dim=1)
@@ -103,7 +105,7 @@ class IncrementalPCA:
         explained_variance = s ** 2 / (n_total - 1)
         explained_variance_ratio = s ** 2 / torch.sum(col_var * n_total)
 
-        p = self.n_components_
+        self.n_components_ = p
         self.n_samples_seen_ = n_total
         self.components_ = vt[:p].contiguous()
         self.singular_values_ = s[:p].contiguous()

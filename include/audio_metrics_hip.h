@@ -40,7 +40,7 @@ typedef enum am_status {
     AM_ERR_BAD_SHAPE = -2,        /* empty input, D < 1, k + 1 > N (torch.kthvalue would raise) */
     AM_ERR_UNSUPPORTED_K = -3,    /* nearest_k > AM_MAX_K in an entry point of the partitioned form */
     AM_ERR_WORKSPACE = -4,        /* workspace missing or too small                            */
-    AM_ERR_NO_CONVERGENCE = -5,   /* Newton-Schulz produced a non-finite trace                 */
+    AM_ERR_NO_CONVERGENCE = -5,   /* Newton-Schulz produced a non-finite trace; Jacobi: non-finite A, or max_sweeps */
     AM_ERR_HIP = -6               /* a HIP runtime call failed (see am_last_error)             */
 } am_status;
 
@@ -636,6 +636,14 @@ int am_kd_rbf_f64(const double* X, int64_t N1, int64_t ldx,
  *                    svd_flip).  One-sided block Jacobi in f64; SYNCHRONISES `stream` once per BLOCK of enqueued
  *                    sweeps (12, then 6 at a time: normally once per solve - the kernels of a sweep return at once when
  *                    the sweep before it applied no rotation; fitting happens once per reference set, not per evaluate).  AM_ERR_NO_CONVERGENCE after max_sweeps (<= 0: 40).
+ *                    Same input, same bits.  Scale: A is brought to unit scale by the power of two of its trace before the
+ *                    first sweep and the eigenvalues are scaled back at the end (both exact), so the result is the
+ *                    same at every scale - evals(2^e A) = 2^e evals(A), evecs equal - for any A whose trace is a finite
+ *                    normal number: largest eigenvalue from 2^-1022 up to trace A < 2^1024.  Entries that fall below
+ *                    2^-1074 trace A are flushed to zero by the scaling (they are below the rounding of the result).
+ *                    Non-finite input: a NaN or an infinity anywhere in A, or a trace that overflows, returns
+ *                    AM_ERR_NO_CONVERGENCE - the status am_frechet_f64 gives a non-finite product - after one
+ *                    synchronisation; no sweep runs and evals / evecs are NOT written.
  *   am_project_f64   out[N][p] (f64) = (X[n][:] - mean[:]) . components[j][:]  - IncrementalPCA.transform - on the f64
  *                    matrix cores; X is the N x D f32 embedding matrix (am_project_rows_f64: f64), mean f64[D], components f64[p][D].
  * ------------------------------------------------------------------------- */
