@@ -19,7 +19,13 @@
 //
 // am_mmd_rbf_f32: Sxx, Syy (ordered pairs i != j: upper-triangular tiles, off-diagonal tiles weighted 2, the valid
 //   diagonal dropped) and Sxy (all tiles) of K = exp(-d2 gamma) in f64.  One f64 partial per workgroup, written to its own
-//   slot and summed by a one-workgroup kernel in a fixed order: identical inputs give identical bits.
+//   slot and summed by one workgroup in a fixed order (mmd_multi_reduce_kernel, through launch_mmd_reduce): identical inputs
+//   give identical bits.  (kad_mmd_kernel is the Gaussian one-scale case of mmd_multi_kernel in all but 0.15 % of run time:
+//   routed through that kernel, mmd_rbf_sums at 20 000 x 20 000 x 512 took 7.280 ms against 7.270 ms, so it stays.)
+//
+// This file also defines what the family shares and kad_common.h declares: the f32 norms and the scan kernel behind their
+// launchers, the chunk rules, the grid plan of the three whole-set blocks, the workspace carves and the validation of two f32
+// sets.
 #include "am_common.h"
 #include "kad_common.h"
 #include "pairwise_common.h"
@@ -27,18 +33,9 @@
 
 namespace am {
 
-constexpr int KAD_BINS = 2048;                       // 11-bit first digit; the 10-bit digits use the lower half
-constexpr int KAD_PASSES = 3;
-constexpr int KAD_AGG_ROUNDS = 3;
 // 73 728 B of staging slabs + 8 192 B of counters = 81 920 B: exactly two workgroups in a CU's 160 KiB
 constexpr size_t KAD_SELECT_LDS_BYTES = ENGINE_LDS_FLOATS * sizeof(float) + KAD_BINS * sizeof(unsigned);
 constexpr size_t KAD_MMD_LDS_BYTES = ENGINE_LDS_FLOATS * sizeof(float);
-
-struct SelectState {                                 // written by the scan kernel of pass p, read by pass p + 1
-    unsigned long long rank;                         // rank inside the keys that share `prefix`
-    unsigned prefix;                                 // the digits fixed so far (11, 21, 31 bits)
-    unsigned pad;
-};
 
 // out[i] = |X[i]|^2 in f64 (one wave per row)
 __global__ void __launch_bounds__(256) kad_norms_kernel(const float* __restrict__ X, int64_t ld, int D, int64_t N,
@@ -55,23 +52,6 @@ __global__ void __launch_bounds__(256) kad_norms_kernel(const float* __restrict_
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off);
     if (lane == 0) out[e] = acc;
-}
-
-// hist[digit] += 1 for every lane with `live` set, equal digits of a wave combined first
-__device__ __forceinline__ void hist_add(unsigned* __restrict__ hist, unsigned digit, bool live, int lane) {
-    unsigned long long todo = __ballot(live);
-#pragma unroll
-    for (int round = 0; round < KAD_AGG_ROUNDS; ++round) {
-        if (todo == 0ull) return;                                        // wave-uniform
-        const int leader = __ffsll((long long)todo) - 1;
-        const unsigned d = (unsigned)__builtin_amdgcn_readlane((int)digit, leader);
-        const bool same = live && digit == d;
-        const unsigned long long mask = __ballot(same);
-        if (lane == leader) atomicAdd(hist + d, (unsigned)__popcll(mask));
-        live = live && !same;
-        todo &= ~mask;
-    }
-    if (live) atomicAdd(hist + digit, 1u);
 }
 
 template <int PASS>
@@ -104,6 +84,8 @@ struct SelectEpilogue {
                     kf = kf < INFINITY ? kf : INFINITY;                 // NaN (a non-finite row) and overflow: +inf
                     const unsigned key = __float_as_uint(kf) & 0x7fffffffu;
                     bool live = qok && pok[nt] && (!diag || p > q);
+                    // (the digits stay in line here and in kad64_select_kernel: behind a shared helper, by value or by
+                    // reference, both kernels compile to other code - 1% more or fewer instructions, two more registers)
                     unsigned digit;
                     if constexpr (PASS == 0) {
                         digit = key >> 20;
@@ -195,49 +177,6 @@ __global__ void __launch_bounds__(256) kad_scan_kernel(const unsigned long long*
     }
 }
 
-// Q tiles per workgroup (kad_common.h)
-int kad_chunk(int64_t tiles_total, int64_t q_tiles) {
-    int64_t ch = std::min<int64_t>(KAD_MAX_CHUNK, std::max<int64_t>(1, tiles_total / 2048));
-    while (ceil_div(q_tiles, ch) > 65535) ch *= 2;
-    return (int)ch;
-}
-
-bool kad_too_large(int64_t N, int64_t ld) { return (uint64_t)N * (uint64_t)ld * 4u >= 0xffffffffull; }
-
-int launch_kad_norms(const float* X, int64_t ld, int D, int64_t N, double* out, hipStream_t st) {
-    hipLaunchKernelGGL(kad_norms_kernel, dim3((unsigned)ceil_div(N, 4)), dim3(256), 0, st, X, ld, D, N, out);
-    AM_LAUNCH_CHECK();
-    return AM_OK;
-}
-
-static size_t select_ws(int64_t N) {
-    Carver c(nullptr, 0);
-    c.take<double>((size_t)N);
-    c.take<unsigned long long>((size_t)KAD_PASSES * KAD_BINS);
-    c.take<SelectState>(1);
-    return c.off;
-}
-
-template <int PASS>
-static int launch_select_pass(const float* X, int64_t N, int64_t ld, int D, const double* norm, int chunk, SelectState* state,
-                              unsigned long long* bins, unsigned long long rank0, float* out, hipStream_t st) {
-    const int64_t T = ceil_div(N, TB);
-    const dim3 grid((unsigned)T, (unsigned)ceil_div(T, chunk));
-    auto launch = [&](auto kernel) -> int {
-        AM_HIP_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), (int)KAD_SELECT_LDS_BYTES));
-        hipLaunchKernelGGL(kernel, grid, dim3(ENGINE_THREADS), KAD_SELECT_LDS_BYTES, st, X, N, ld, D, norm, chunk,
-                           (const SelectState*)state, bins + (size_t)PASS * KAD_BINS);
-        AM_LAUNCH_CHECK();
-        return AM_OK;
-    };
-    const int rc = (D % BK) != 0 ? launch(&kad_select_kernel<PASS, true>) : launch(&kad_select_kernel<PASS, false>);
-    if (rc != AM_OK) return rc;
-    hipLaunchKernelGGL(kad_scan_kernel<PASS>, dim3(1), dim3(256), 0, st, (const unsigned long long*)(bins + (size_t)PASS * KAD_BINS),
-                       state, rank0, out);
-    AM_LAUNCH_CHECK();
-    return AM_OK;
-}
-
 // ------------------------------------------------------------------------------------------------ kernel sums
 
 struct MmdEpilogue {
@@ -318,25 +257,60 @@ kad_mmd_kernel(const float* __restrict__ Q, int64_t nq, int64_t ldq, const doubl
     if (L.tid == 0) partial[slot] = ((red[0] + red[1]) + red[2]) + red[3];
 }
 
-// out[0] = sum of partial[0 .. count) in a fixed order: strided per-thread sums, then a tree
-__global__ void __launch_bounds__(256) kad_reduce_kernel(const double* __restrict__ partial, int64_t count, double* __restrict__ out) {
-    __shared__ double red[256];
-    const int tid = threadIdx.x;
-    double s = 0.0;
-    for (int64_t i = tid; i < count; i += 256) s += partial[i];
-    red[tid] = s;
-    __syncthreads();
-    for (int w = 128; w >= 1; w >>= 1) {
-        if (tid < w) red[tid] += red[tid + w];
-        __syncthreads();
-    }
-    if (tid == 0) out[0] = red[0];
+// Q tiles per workgroup (kad_common.h)
+int kad_chunk(int64_t tiles_total, int64_t q_tiles) {
+    int64_t ch = std::min<int64_t>(KAD_MAX_CHUNK, std::max<int64_t>(1, tiles_total / 2048));
+    while (ceil_div(q_tiles, ch) > 65535) ch *= 2;
+    return (int)ch;
 }
 
-// the grids of the three blocks (kad_common.h)
-MmdPlan mmd_plan(int64_t N1, int64_t N2) {
+bool kad_too_large(int64_t N, int64_t ld) { return (uint64_t)N * (uint64_t)ld * 4u >= 0xffffffffull; }
+
+int launch_kad_norms(const float* X, int64_t ld, int D, int64_t N, double* out, hipStream_t st) {
+    hipLaunchKernelGGL(kad_norms_kernel, dim3((unsigned)ceil_div(N, 4)), dim3(256), 0, st, X, ld, D, N, out);
+    AM_LAUNCH_CHECK();
+    return AM_OK;
+}
+
+int launch_kad_scan(int pass, const unsigned long long* bins, SelectState* state, unsigned long long rank0, float* out, hipStream_t st) {
+    auto kernel = pass == 0 ? &kad_scan_kernel<0> : pass == 1 ? &kad_scan_kernel<1> : &kad_scan_kernel<2>;
+    hipLaunchKernelGGL(kernel, dim3(1), dim3(256), 0, st, bins, state, rank0, out);
+    AM_LAUNCH_CHECK();
+    return AM_OK;
+}
+
+SelectWs select_carve(void* ws, size_t ws_bytes, int64_t N) {
+    Carver c(ws, ws_bytes);
+    SelectWs w{};
+    w.norm = c.take<double>((size_t)N);
+    w.bins = c.take<unsigned long long>((size_t)KAD_PASSES * KAD_BINS);
+    w.state = c.take<SelectState>(1);
+    w.bytes = c.off;
+    w.ok = c.ok();
+    return w;
+}
+
+template <int PASS>
+static int launch_select_pass(const float* X, int64_t N, int64_t ld, int D, const double* norm, int chunk, SelectState* state,
+                              unsigned long long* bins, unsigned long long rank0, float* out, hipStream_t st) {
+    const int64_t T = ceil_div(N, TB);
+    const dim3 grid((unsigned)T, (unsigned)ceil_div(T, chunk));
+    auto launch = [&](auto kernel) -> int {
+        AM_HIP_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), (int)KAD_SELECT_LDS_BYTES));
+        hipLaunchKernelGGL(kernel, grid, dim3(ENGINE_THREADS), KAD_SELECT_LDS_BYTES, st, X, N, ld, D, norm, chunk,
+                           (const SelectState*)state, bins + (size_t)PASS * KAD_BINS);
+        AM_LAUNCH_CHECK();
+        return AM_OK;
+    };
+    const int rc = (D % BK) != 0 ? launch(&kad_select_kernel<PASS, true>) : launch(&kad_select_kernel<PASS, false>);
+    if (rc != AM_OK) return rc;
+    return launch_kad_scan(PASS, bins + (size_t)PASS * KAD_BINS, state, rank0, out, st);
+}
+
+// ------------------------------------------------------------------------------------------------ shared host side (kad_common.h)
+MmdPlan mmd_plan(int64_t N1, int64_t N2, int tile_rows) {
     MmdPlan p;
-    const int64_t T1 = ceil_div(N1, TB), T2 = ceil_div(N2, TB);
+    const int64_t T1 = ceil_div(N1, tile_rows), T2 = ceil_div(N2, tile_rows);
     const int64_t tq[3] = {T1, T2, T1}, tp[3] = {T1, T2, T2};
     for (int b = 0; b < 3; ++b) {
         const int64_t total = b < 2 ? tp[b] * (tp[b] + 1) / 2 : tq[b] * tp[b];
@@ -347,22 +321,59 @@ MmdPlan mmd_plan(int64_t N1, int64_t N2) {
     return p;
 }
 
-struct MmdWs {
-    double *n1, *n2, *partial[3];
-    size_t bytes;
-    bool ok;
-};
+SetNorms carve_set_norms(Carver& c, int64_t N1, int64_t N2, unsigned blocks) {
+    SetNorms n{};
+    if (blocks & (AM_MMD_XX | AM_MMD_XY)) n.n1 = c.take<double>((size_t)N1);
+    if (blocks & (AM_MMD_YY | AM_MMD_XY)) n.n2 = c.take<double>((size_t)N2);
+    return n;
+}
 
-static MmdWs mmd_carve(void* ws, size_t ws_bytes, int64_t N1, int64_t N2, unsigned blocks, const MmdPlan& plan) {
+int launch_set_norms(const float* X, int64_t N1, int64_t ldx, const float* Y, int64_t N2, int64_t ldy, int D, const SetNorms& n,
+                     hipStream_t st) {
+    int rc = n.n1 ? launch_kad_norms(X, ldx, D, N1, n.n1, st) : AM_OK;
+    if (rc == AM_OK && n.n2) rc = launch_kad_norms(Y, ldy, D, N2, n.n2, st);
+    return rc;
+}
+
+MmdWs mmd_carve(void* ws, size_t ws_bytes, int64_t N1, int64_t N2, int nscales, unsigned blocks, const MmdPlan& plan) {
     Carver c(ws, ws_bytes);
     MmdWs w{};
-    if (blocks & (AM_MMD_XX | AM_MMD_XY)) w.n1 = c.take<double>((size_t)N1);
-    if (blocks & (AM_MMD_YY | AM_MMD_XY)) w.n2 = c.take<double>((size_t)N2);
+    w.n = carve_set_norms(c, N1, N2, blocks);
     for (int b = 0; b < 3; ++b)
-        if (blocks & (1u << b)) w.partial[b] = c.take<double>(plan.slots[b]);
+        if (blocks & (1u << b)) w.partial[b] = c.take<double>(plan.slots[b] * (size_t)nscales);
     w.bytes = c.off;
     w.ok = c.ok();
     return w;
+}
+
+int kadg_cross_chunk(int64_t TP, int64_t TQ) {
+    const int64_t cap = std::max<int64_t>(KADG_CROSS_CHUNKS, KADG_CROSS_SLOTS / TP);
+    return (int)std::max<int64_t>(kad_chunk(TP * TQ, TQ), ceil_div(TQ, cap));
+}
+
+int64_t kadg_within_span(const int64_t* offsets, int64_t TP, int64_t n_total, int tile_rows) {
+    int64_t span = 1;
+    for (int64_t t = 0, g0 = 0, g1 = 0; t < TP; ++t) {
+        const int64_t pfirst = t * tile_rows, plast = std::min<int64_t>(pfirst + tile_rows, n_total) - 1;
+        while (offsets[g0 + 1] <= pfirst) ++g0;
+        g1 = std::max(g1, g0);
+        while (offsets[g1 + 1] <= plast) ++g1;
+        span = std::max<int64_t>(span, (offsets[g1 + 1] - 1) / tile_rows - offsets[g0] / tile_rows + 1);
+    }
+    return span;
+}
+
+int kadg_within_chunk(int64_t span) { return (int)std::max<int64_t>(KAD_MAX_CHUNK, ceil_div(span, KADG_WITHIN_CHUNKS)); }
+
+int check_two_sets_f32(const float* X, int64_t N1, int64_t ldx, const float* Y, int64_t N2, int64_t ldy, int D, unsigned blocks) {
+    AM_REQUIRE(X && Y, AM_ERR_BAD_ARG, "null pointer");
+    AM_REQUIRE(blocks != 0 && (blocks & ~7u) == 0, AM_ERR_BAD_ARG, "blocks = %u is not a mask of AM_MMD_XX | AM_MMD_YY | AM_MMD_XY", blocks);
+    AM_REQUIRE(N1 >= 1 && N2 >= 1 && D >= 1, AM_ERR_BAD_SHAPE, "N1=%lld N2=%lld D=%d", (long long)N1, (long long)N2, D);
+    AM_REQUIRE(aligned16(X) && aligned16(Y) && ldx % 4 == 0 && ldy % 4 == 0 && ldx >= D && ldy >= D, AM_ERR_BAD_ARG,
+               "X/Y must be 16-byte aligned with ld %% 4 == 0 and ld >= D");
+    AM_REQUIRE(!kad_too_large(N1, ldx) && !kad_too_large(N2, ldy), AM_ERR_BAD_SHAPE,
+               "N * ld * 4 bytes of a set >= 4 GiB: one buffer descriptor spans a matrix");
+    return AM_OK;
 }
 
 }  // namespace am
@@ -371,7 +382,7 @@ using namespace am;
 
 extern "C" size_t am_pairwise_select_workspace_bytes(int64_t N, int D) {
     if (N < 2 || D < 1) return 0;
-    return select_ws(N);
+    return select_carve(nullptr, 0, N).bytes;
 }
 
 extern "C" int am_pairwise_select_f32(const float* X, int64_t N, int64_t ld, int D, int64_t rank, float* out_d2, void* ws,
@@ -385,60 +396,50 @@ extern "C" int am_pairwise_select_f32(const float* X, int64_t N, int64_t ld, int
     const int64_t pairs = N * (N - 1) / 2;               // N < 2^28 (ld >= 4): no overflow
     AM_REQUIRE(rank < pairs, AM_ERR_BAD_SHAPE, "rank %lld of %lld pairs", (long long)rank, (long long)pairs);
     if (rank < 0) rank = (pairs - 1) / 2;                // lower median (torch.median's convention)
-    Carver c(ws, ws_bytes);
-    double* norm = c.take<double>((size_t)N);
-    unsigned long long* bins = c.take<unsigned long long>((size_t)KAD_PASSES * KAD_BINS);
-    SelectState* state = c.take<SelectState>(1);
-    AM_REQUIRE(c.ok(), AM_ERR_WORKSPACE, "workspace too small: need %zu bytes (am_pairwise_select_workspace_bytes), have %zu", c.off,
+    const SelectWs w = select_carve(ws, ws_bytes, N);
+    AM_REQUIRE(w.ok, AM_ERR_WORKSPACE, "workspace too small: need %zu bytes (am_pairwise_select_workspace_bytes), have %zu", w.bytes,
                ws_bytes);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    AM_HIP_TRY(hipMemsetAsync(bins, 0, (size_t)KAD_PASSES * KAD_BINS * sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(kad_norms_kernel, dim3((unsigned)ceil_div(N, 4)), dim3(256), 0, st, X, ld, D, N, norm);
-    AM_LAUNCH_CHECK();
+    AM_HIP_TRY(hipMemsetAsync(w.bins, 0, (size_t)KAD_PASSES * KAD_BINS * sizeof(unsigned long long), st));
+    int rc = launch_kad_norms(X, ld, D, N, w.norm, st);
     const int64_t T = ceil_div(N, TB);
     const int chunk = kad_chunk(T * (T + 1) / 2, T);
-    int rc = launch_select_pass<0>(X, N, ld, D, norm, chunk, state, bins, (unsigned long long)rank, out_d2, st);
-    if (rc == AM_OK) rc = launch_select_pass<1>(X, N, ld, D, norm, chunk, state, bins, 0ull, out_d2, st);
-    if (rc == AM_OK) rc = launch_select_pass<2>(X, N, ld, D, norm, chunk, state, bins, 0ull, out_d2, st);
+    if (rc == AM_OK) rc = launch_select_pass<0>(X, N, ld, D, w.norm, chunk, w.state, w.bins, (unsigned long long)rank, out_d2, st);
+    if (rc == AM_OK) rc = launch_select_pass<1>(X, N, ld, D, w.norm, chunk, w.state, w.bins, 0ull, out_d2, st);
+    if (rc == AM_OK) rc = launch_select_pass<2>(X, N, ld, D, w.norm, chunk, w.state, w.bins, 0ull, out_d2, st);
     return rc;
 }
 
 extern "C" size_t am_mmd_rbf_workspace_bytes(int64_t N1, int64_t N2, int D, unsigned blocks) {
     if (N1 < 1 || N2 < 1 || D < 1 || (blocks & 7u) == 0) return 0;
-    return mmd_carve(nullptr, 0, N1, N2, blocks & 7u, mmd_plan(N1, N2)).bytes;
+    return mmd_carve(nullptr, 0, N1, N2, 1, blocks & 7u, mmd_plan(N1, N2, TB)).bytes;
 }
 
 extern "C" int am_mmd_rbf_f32(const float* X, int64_t N1, int64_t ldx, const float* Y, int64_t N2, int64_t ldy, int D,
                               const float* bw2_dev, double gamma, unsigned blocks, double* out_sums, void* ws, size_t ws_bytes,
                               am_stream_t stream) {
-    AM_REQUIRE(X && Y && out_sums, AM_ERR_BAD_ARG, "null pointer");
-    AM_REQUIRE(blocks != 0 && (blocks & ~7u) == 0, AM_ERR_BAD_ARG, "blocks = %u is not a mask of AM_MMD_XX | AM_MMD_YY | AM_MMD_XY", blocks);
-    AM_REQUIRE(N1 >= 1 && N2 >= 1 && D >= 1, AM_ERR_BAD_SHAPE, "N1=%lld N2=%lld D=%d", (long long)N1, (long long)N2, D);
-    AM_REQUIRE(aligned16(X) && aligned16(Y) && ldx % 4 == 0 && ldy % 4 == 0 && ldx >= D && ldy >= D, AM_ERR_BAD_ARG,
-               "X/Y must be 16-byte aligned with ld %% 4 == 0 and ld >= D");
-    AM_REQUIRE(!kad_too_large(N1, ldx) && !kad_too_large(N2, ldy), AM_ERR_BAD_SHAPE,
-               "N * ld * 4 bytes of a set >= 4 GiB: one buffer descriptor spans a matrix");
+    AM_REQUIRE(out_sums, AM_ERR_BAD_ARG, "null pointer");
+    int rc = check_two_sets_f32(X, N1, ldx, Y, N2, ldy, D, blocks);
+    if (rc != AM_OK) return rc;
     AM_REQUIRE(bw2_dev != nullptr || gamma >= 0.0, AM_ERR_BAD_ARG, "gamma must be >= 0 (or bw2_dev given)");
-    const MmdPlan plan = mmd_plan(N1, N2);
-    const MmdWs w = mmd_carve(ws, ws_bytes, N1, N2, blocks, plan);
+    const MmdPlan plan = mmd_plan(N1, N2, TB);
+    const MmdWs w = mmd_carve(ws, ws_bytes, N1, N2, 1, blocks, plan);
     AM_REQUIRE(w.ok, AM_ERR_WORKSPACE, "workspace too small: need %zu bytes (am_mmd_rbf_workspace_bytes), have %zu", w.bytes, ws_bytes);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (w.n1) hipLaunchKernelGGL(kad_norms_kernel, dim3((unsigned)ceil_div(N1, 4)), dim3(256), 0, st, X, ldx, D, N1, w.n1);
-    if (w.n2) hipLaunchKernelGGL(kad_norms_kernel, dim3((unsigned)ceil_div(N2, 4)), dim3(256), 0, st, Y, ldy, D, N2, w.n2);
-    AM_LAUNCH_CHECK();
+    rc = launch_set_norms(X, N1, ldx, Y, N2, ldy, D, w.n, st);
+    if (rc != AM_OK) return rc;
     auto launch = [&](auto kernel) -> int {
         AM_HIP_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), (int)KAD_MMD_LDS_BYTES));
         for (int b = 0; b < 3; ++b) {
             if (!(blocks & (1u << b))) continue;
             const bool q_is_y = b == 1, p_is_x = b == 0;
             hipLaunchKernelGGL(kernel, plan.grid[b], dim3(ENGINE_THREADS), KAD_MMD_LDS_BYTES, st,
-                               q_is_y ? Y : X, q_is_y ? N2 : N1, q_is_y ? ldy : ldx, (const double*)(q_is_y ? w.n2 : w.n1),
-                               p_is_x ? X : Y, p_is_x ? N1 : N2, p_is_x ? ldx : ldy, (const double*)(p_is_x ? w.n1 : w.n2),
+                               q_is_y ? Y : X, q_is_y ? N2 : N1, q_is_y ? ldy : ldx, (const double*)(q_is_y ? w.n.n2 : w.n.n1),
+                               p_is_x ? X : Y, p_is_x ? N1 : N2, p_is_x ? ldx : ldy, (const double*)(p_is_x ? w.n.n1 : w.n.n2),
                                D, b < 2 ? 1 : 0, plan.chunk[b], bw2_dev, gamma, w.partial[b]);
             AM_LAUNCH_CHECK();
-            hipLaunchKernelGGL(kad_reduce_kernel, dim3(1), dim3(256), 0, st, (const double*)w.partial[b], (int64_t)plan.slots[b],
-                               out_sums + b);
-            AM_LAUNCH_CHECK();
+            const int rr = launch_mmd_reduce(w.partial[b], (int64_t)plan.slots[b], 1, out_sums + b, st);
+            if (rr != AM_OK) return rr;
         }
         return AM_OK;
     };

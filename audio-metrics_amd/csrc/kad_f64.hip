@@ -12,9 +12,11 @@
 //   bits(rn32(d2)), NaN and overflow +inf; three radix passes of 11 / 10 / 10 bits over the upper-triangular tiles (P tile
 //   tp against Q tiles 0 .. tp, a pair counts where p > q), a per-workgroup LDS histogram flushed once into 64-bit global
 //   bins, a one-workgroup scan between passes, no host synchronisation.  Equal digits of a wave are combined before any
-//   LDS atomic (kad64_hist_add: the reasoning is at the head of kad.hip).
+//   LDS atomic (hist_add: the reasoning is at the head of kad.hip).
 // am_mmd_rbf_f64: Sxx, Syy (upper-triangular tiles, off-diagonal tiles weighted 2, diagonal entries dropped) and Sxy; one
 //   f64 partial per workgroup in a slot of its own, summed by one workgroup in a fixed order: no atomics, same bits.
+// Nothing that is independent of the element type is repeated here: the select's state, digits and scan, the reduce kernel,
+// the grid plan, the chunk rules and the workspace carves are those of the f32 forms (kad_common.h), at 64-row tiles.
 // am_mmd_rbf_groups_f64: the contract of kad_groups.hip by LIST POSITION p < n_total:
 //   kadg64_prep_kernel    per position: its stored row (-1 for an index outside [0, N1): never dereferenced, the position
 //                         goes to the flag word, the row counts as zeros), its squared norm and its group; the tail up to
@@ -24,8 +26,8 @@
 //                         own groups gathered the same way (within: masked by gid[q] == gid[p] && q != p).  In this engine
 //                         everything a lane accumulates belongs to ONE P row: a lane keeps one running sum, and the four
 //                         lanes of a row (l4 = 0 .. 3) are added in a fixed order at the end -> partial[chunk][position]
-//   kadg64_rowsum_kernel  per position: its chunks in chunk order -> rows[p] = {w_p, c_p}
-//   kadg64_finish_kernel  one workgroup per group: strided per-thread sums, then a tree -> out_groups[b] = {Sxx_b, Sxy_b}
+//   kadg_rowsum_kernel    per position: its chunks in chunk order -> rows[p] = {w_p, c_p}               (kad_groups.hip)
+//   kadg_finish_kernel    one workgroup per group: strided per-thread sums, then a tree -> out_groups[b] = {Sxx_b, Sxy_b}
 //   The result depends on the list order only; two calls give the same bits.
 // Rows need no alignment (8-byte loads) and no buffer descriptor is used: the 4 GiB limit of the f32 forms does not apply.
 #include "am_common.h"
@@ -35,19 +37,6 @@
 #include <algorithm>
 
 namespace am {
-
-constexpr int KAD64_BINS = 2048;                     // 11-bit first digit; the 10-bit digits use the lower half
-constexpr int KAD64_PASSES = 3;
-constexpr int KAD64_AGG_ROUNDS = 3;
-constexpr int KADG64_WITHIN_CHUNKS = 4;              // most Q chunks of a P tile in the within pass
-constexpr int64_t KADG64_CROSS_CHUNKS = 64;          // most Q chunks of the cross pass once there are many P tiles ...
-constexpr int64_t KADG64_CROSS_SLOTS = 4096;         // ... (P tiles) x (chunks) may reach this with few P tiles
-
-struct Select64State {                               // written by the scan kernel of pass p, read by pass p + 1
-    unsigned long long rank;                         // rank inside the keys that share `prefix`
-    unsigned prefix;                                 // the digits fixed so far (11, 21, 31 bits)
-    unsigned pad;
-};
 
 // out[i] = |X[i]|^2 (one wave per row, fixed order: the loop of row_sqnorm64_kernel)
 __device__ __forceinline__ double kad64_sqnorm(const double* __restrict__ x, int D, int lane) {
@@ -68,38 +57,21 @@ __global__ void __launch_bounds__(256) kad64_norms_kernel(const double* __restri
     if (lane == 0) out[row] = s;
 }
 
-// hist[digit] += 1 for every lane with `live` set, equal digits of a wave combined first
-__device__ __forceinline__ void kad64_hist_add(unsigned* __restrict__ hist, unsigned digit, bool live, int lane) {
-    unsigned long long todo = __ballot(live);
-#pragma unroll
-    for (int round = 0; round < KAD64_AGG_ROUNDS; ++round) {
-        if (todo == 0ull) return;                                        // wave-uniform
-        const int leader = __ffsll((long long)todo) - 1;
-        const unsigned d = (unsigned)__builtin_amdgcn_readlane((int)digit, leader);
-        const bool same = live && digit == d;
-        const unsigned long long mask = __ballot(same);
-        if (lane == leader) atomicAdd(hist + d, (unsigned)__popcll(mask));
-        live = live && !same;
-        todo &= ~mask;
-    }
-    if (live) atomicAdd(hist + digit, 1u);
-}
-
 // grid: x = P tile (heaviest first), y = chunk of `chunk_tiles` Q tiles; chunks past the diagonal have nothing to do
 template <int PASS>
 __global__ void __launch_bounds__(FTHREADS)
 kad64_select_kernel(const double* __restrict__ X, int64_t N, int64_t ld, int D, const double* __restrict__ norm, int chunk_tiles,
-                    const Select64State* __restrict__ state, unsigned long long* __restrict__ bins) {
+                    const SelectState* __restrict__ state, unsigned long long* __restrict__ bins) {
     __shared__ __attribute__((aligned(16))) double stages[FENGINE_DOUBLES];
     __shared__ double qnorm[FT];
-    __shared__ unsigned hist[KAD64_BINS];
+    __shared__ unsigned hist[KAD_BINS];
     const FLane L;
     const int64_t T = (N + FT - 1) / FT;
     const int64_t tp = T - 1 - (int64_t)blockIdx.x;
     const int64_t q0 = (int64_t)blockIdx.y * chunk_tiles;
     if (q0 > tp) return;
     const int64_t q1 = q0 + chunk_tiles < tp + 1 ? q0 + chunk_tiles : tp + 1;
-    for (int b = L.tid; b < KAD64_BINS; b += FTHREADS) hist[b] = 0u;      // visible after the first barrier of the first tile
+    for (int b = L.tid; b < KAD_BINS; b += FTHREADS) hist[b] = 0u;      // visible after the first barrier of the first tile
     const unsigned prefix = PASS == 0 ? 0u : state->prefix;
     const int64_t p = tp * FT + L.prow();
     const bool pok = p < N;
@@ -123,7 +95,7 @@ kad64_select_kernel(const double* __restrict__ X, int64_t N, int64_t ld, int D, 
                 kf = kf < INFINITY ? kf : INFINITY;                     // overflow: +inf (a NaN is +inf already)
                 const unsigned key = __float_as_uint(kf) & 0x7fffffffu;
                 bool live = pok && t * FT + qr < p;                     // each unordered pair once (q < p < N)
-                unsigned digit;
+                unsigned digit;                                         // (in line, as in kad.hip)
                 if constexpr (PASS == 0) {
                     digit = key >> 20;
                 } else if constexpr (PASS == 1) {
@@ -133,67 +105,24 @@ kad64_select_kernel(const double* __restrict__ X, int64_t N, int64_t ld, int D, 
                     live = live && (key >> 10) == prefix;
                     digit = key & 1023u;
                 }
-                kad64_hist_add(hist, digit, live, L.lane);
+                hist_add(hist, digit, live, L.lane);
             }
         __syncthreads();                                                // qnorm is rewritten by the next tile; the counters are complete
     }
-    for (int b = L.tid; b < KAD64_BINS; b += FTHREADS) {                  // one global flush per workgroup
+    for (int b = L.tid; b < KAD_BINS; b += FTHREADS) {                  // one global flush per workgroup
         const unsigned c = hist[b];
         if (c != 0u) atomicAdd(bins + b, (unsigned long long)c);
     }
 }
 
-// One workgroup: the bin that holds the wanted rank -> next prefix, rank inside that bin; the last pass writes the value.
 template <int PASS>
-__global__ void __launch_bounds__(256) kad64_scan_kernel(const unsigned long long* __restrict__ bins, Select64State* state,
-                                                         unsigned long long rank0, float* __restrict__ out) {
-    __shared__ unsigned long long part[256];
-    const int tid = threadIdx.x;
-    constexpr int PER = KAD64_BINS / 256;
-    unsigned long long c[PER], sum = 0ull;
-#pragma unroll
-    for (int j = 0; j < PER; ++j) {
-        c[j] = bins[tid * PER + j];
-        sum += c[j];
-    }
-    part[tid] = sum;
-    const unsigned long long rank = PASS == 0 ? rank0 : state->rank;
-    const unsigned prefix = PASS == 0 ? 0u : state->prefix;
-    __syncthreads();                                  // every thread holds the old state before one of them replaces it
-    if (tid == 0) {
-        unsigned long long run = 0ull;
-        for (int t = 0; t < 256; ++t) {
-            const unsigned long long v = part[t];
-            part[t] = run;
-            run += v;
-        }
-    }
-    __syncthreads();
-    unsigned long long cum = part[tid];
-#pragma unroll
-    for (int j = 0; j < PER; ++j) {
-        if (rank >= cum && rank < cum + c[j]) {       // exactly one (thread, j): the bins hold every pair once
-            const unsigned digit = (unsigned)(tid * PER + j);
-            const unsigned next = PASS == 0 ? digit : ((prefix << 10) | digit);
-            state->rank = rank - cum;
-            state->prefix = next;
-            if (PASS == KAD64_PASSES - 1) *out = __uint_as_float(next);
-        }
-        cum += c[j];
-    }
-}
-
-template <int PASS>
-static int launch_select64_pass(const double* X, int64_t N, int64_t ld, int D, const double* norm, int chunk, Select64State* state,
+static int launch_select64_pass(const double* X, int64_t N, int64_t ld, int D, const double* norm, int chunk, SelectState* state,
                                 unsigned long long* bins, unsigned long long rank0, float* out, hipStream_t st) {
     const int64_t T = ceil_div(N, FT);
     hipLaunchKernelGGL(kad64_select_kernel<PASS>, dim3((unsigned)T, (unsigned)ceil_div(T, chunk)), dim3(FTHREADS), 0, st, X, N, ld, D, norm,
-                       chunk, (const Select64State*)state, bins + (size_t)PASS * KAD64_BINS);
+                       chunk, (const SelectState*)state, bins + (size_t)PASS * KAD_BINS);
     AM_LAUNCH_CHECK();
-    hipLaunchKernelGGL(kad64_scan_kernel<PASS>, dim3(1), dim3(256), 0, st, (const unsigned long long*)(bins + (size_t)PASS * KAD64_BINS),
-                       state, rank0, out);
-    AM_LAUNCH_CHECK();
-    return AM_OK;
+    return launch_kad_scan(PASS, bins + (size_t)PASS * KAD_BINS, state, rank0, out, st);
 }
 
 // ------------------------------------------------------------------------------------------------ kernel sums
@@ -254,70 +183,7 @@ kad64_mmd_kernel(const double* __restrict__ Q, int64_t nq, int64_t ldq, const do
     if (L.tid == 0) partial[slot] = ((red[0] + red[1]) + red[2]) + red[3];
 }
 
-// out[0] = sum of partial[0 .. count) in a fixed order: strided per-thread sums, then a tree
-__global__ void __launch_bounds__(256) kad64_reduce_kernel(const double* __restrict__ partial, int64_t count, double* __restrict__ out) {
-    __shared__ double red[256];
-    const int tid = threadIdx.x;
-    double s = 0.0;
-    for (int64_t i = tid; i < count; i += 256) s += partial[i];
-    red[tid] = s;
-    __syncthreads();
-    for (int w = 128; w >= 1; w >>= 1) {
-        if (tid < w) red[tid] += red[tid + w];
-        __syncthreads();
-    }
-    if (tid == 0) out[0] = red[0];
-}
-
-struct Mmd64Plan {
-    int chunk[3];
-    dim3 grid[3];
-    size_t slots[3];
-};
-
-static Mmd64Plan mmd64_plan(int64_t N1, int64_t N2) {
-    Mmd64Plan p;
-    const int64_t T1 = ceil_div(N1, FT), T2 = ceil_div(N2, FT);
-    const int64_t tq[3] = {T1, T2, T1}, tp[3] = {T1, T2, T2};
-    for (int b = 0; b < 3; ++b) {
-        const int64_t total = b < 2 ? tp[b] * (tp[b] + 1) / 2 : tq[b] * tp[b];
-        p.chunk[b] = kad_chunk(total, tq[b]);
-        p.grid[b] = dim3((unsigned)tp[b], (unsigned)ceil_div(tq[b], p.chunk[b]));
-        p.slots[b] = (size_t)p.grid[b].x * p.grid[b].y;
-    }
-    return p;
-}
-
-struct Mmd64Ws {
-    double *n1, *n2, *partial[3];
-    size_t bytes;
-    bool ok;
-};
-
-static Mmd64Ws mmd64_carve(void* ws, size_t ws_bytes, int64_t N1, int64_t N2, unsigned blocks, const Mmd64Plan& plan) {
-    Carver c(ws, ws_bytes);
-    Mmd64Ws w{};
-    if (blocks & (AM_MMD_XX | AM_MMD_XY)) w.n1 = c.take<double>((size_t)N1);
-    if (blocks & (AM_MMD_YY | AM_MMD_XY)) w.n2 = c.take<double>((size_t)N2);
-    for (int b = 0; b < 3; ++b)
-        if (blocks & (1u << b)) w.partial[b] = c.take<double>(plan.slots[b]);
-    w.bytes = c.off;
-    w.ok = c.ok();
-    return w;
-}
-
 // ------------------------------------------------------------------------------------------------ per-group sums
-// first group whose end lies past position p (offs: B + 1 entries, offs[0] = 0 <= p < offs[B])
-__device__ __forceinline__ int kadg64_group_of(const int64_t* __restrict__ offs, int B, int64_t p) {
-    int lo = 0, hi = B - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (offs[mid + 1] > p) hi = mid;
-        else lo = mid + 1;
-    }
-    return lo;
-}
-
 // one wave per list position (padding included)
 __global__ void __launch_bounds__(256) kadg64_prep_kernel(const double* __restrict__ X, int64_t N1, int64_t ld, int D,
                                                           const int64_t* __restrict__ idx, const int64_t* __restrict__ offs, int B,
@@ -342,7 +208,7 @@ __global__ void __launch_bounds__(256) kadg64_prep_kernel(const double* __restri
         if (!ok) atomicMax(flag, (unsigned long long)p + 1ull);
         rowof[p] = ok ? row : -1;
         norm[p] = s;
-        gid[p] = kadg64_group_of(offs, B, p);
+        gid[p] = group_of(offs, B, p);
     }
 }
 
@@ -425,46 +291,6 @@ kadg64_rows_kernel(const double* __restrict__ X, int64_t ldx, const int64_t* __r
     if (L.l4 == 0) out[L.prow()] = s2;
 }
 
-// rows[p] = {w_p, c_p}: a position's chunks in chunk order
-__global__ void __launch_bounds__(256) kadg64_rowsum_kernel(const double* __restrict__ pw, int nw, const double* __restrict__ pc, int nc,
-                                                            int64_t n_pad, int64_t n_total, double* __restrict__ rows) {
-    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (p >= n_total) return;
-    double w = 0.0, c = 0.0;
-    for (int j = 0; j < nw; ++j) w += pw[(int64_t)j * n_pad + p];
-    for (int j = 0; j < nc; ++j) c += pc[(int64_t)j * n_pad + p];
-    rows[2 * p] = w;
-    rows[2 * p + 1] = c;
-}
-
-// out[b] = {Sxx_b, Sxy_b}: strided per-thread sums over the group's positions, then a tree
-__global__ void __launch_bounds__(256) kadg64_finish_kernel(const double* __restrict__ rows, const int64_t* __restrict__ offs,
-                                                            double* __restrict__ out) {
-    __shared__ double redw[256], redc[256];
-    const int tid = threadIdx.x;
-    const int64_t b = blockIdx.x;
-    const int64_t p1 = offs[b + 1];
-    double w = 0.0, c = 0.0;
-    for (int64_t p = offs[b] + tid; p < p1; p += 256) {
-        w += rows[2 * p];
-        c += rows[2 * p + 1];
-    }
-    redw[tid] = w;
-    redc[tid] = c;
-    __syncthreads();
-    for (int s = 128; s >= 1; s >>= 1) {
-        if (tid < s) {
-            redw[tid] += redw[tid + s];
-            redc[tid] += redc[tid + s];
-        }
-        __syncthreads();
-    }
-    if (tid == 0) {
-        out[2 * b] = redw[0];
-        out[2 * b + 1] = redc[0];
-    }
-}
-
 struct Groups64Plan {
     int64_t TP, TQ, n_pad;
     int chunk_c, nch_c;          // cross pass
@@ -475,9 +301,7 @@ static Groups64Plan groups64_plan(int64_t n_total, int64_t N2) {
     p.TP = ceil_div(n_total, FT);
     p.TQ = ceil_div(N2, FT);
     p.n_pad = p.TP * FT;
-    // per-ROW partials: 64 doubles per (P tile, chunk), so the number of chunks is capped where the whole-set sums' is not
-    const int64_t cap = std::max<int64_t>(KADG64_CROSS_CHUNKS, KADG64_CROSS_SLOTS / p.TP);
-    p.chunk_c = (int)std::max<int64_t>(kad_chunk(p.TP * p.TQ, p.TQ), ceil_div(p.TQ, cap));
+    p.chunk_c = kadg_cross_chunk(p.TP, p.TQ);            // 64 doubles per (P tile, chunk)
     p.nch_c = (int)ceil_div(p.TQ, p.chunk_c);
     return p;
 }
@@ -496,7 +320,7 @@ static bool groups64_carve(Carver& c, int64_t n_total, int B, int64_t N2, const 
     w.xn = c.take<double>((size_t)p.n_pad);
     w.yn = c.take<double>((size_t)N2);
     w.rows = c.take<double>(2 * (size_t)n_total);
-    w.pw = c.take<double>((size_t)std::min<int64_t>(p.TP, KADG64_WITHIN_CHUNKS) * (size_t)p.n_pad);
+    w.pw = c.take<double>((size_t)std::min<int64_t>(p.TP, KADG_WITHIN_CHUNKS) * (size_t)p.n_pad);
     w.pc = c.take<double>((size_t)p.nch_c * (size_t)p.n_pad);
     return c.ok();
 }
@@ -507,11 +331,7 @@ using namespace am;
 
 extern "C" size_t am_pairwise_select_f64_workspace_bytes(int64_t N, int D) {
     if (N < 2 || D < 1) return 0;
-    Carver c(nullptr, 0);
-    c.take<double>((size_t)N);
-    c.take<unsigned long long>((size_t)KAD64_PASSES * KAD64_BINS);
-    c.take<Select64State>(1);
-    return c.off;
+    return select_carve(nullptr, 0, N).bytes;
 }
 
 extern "C" int am_pairwise_select_f64(const double* X, int64_t N, int64_t ld, int D, int64_t rank, float* out_d2, void* ws,
@@ -524,27 +344,24 @@ extern "C" int am_pairwise_select_f64(const double* X, int64_t N, int64_t ld, in
     const int64_t pairs = N * (N - 1) / 2;
     AM_REQUIRE(rank < pairs, AM_ERR_BAD_SHAPE, "rank %lld of %lld pairs", (long long)rank, (long long)pairs);
     if (rank < 0) rank = (pairs - 1) / 2;                // lower median (torch.median's convention)
-    Carver c(ws, ws_bytes);
-    double* norm = c.take<double>((size_t)N);
-    unsigned long long* bins = c.take<unsigned long long>((size_t)KAD64_PASSES * KAD64_BINS);
-    Select64State* state = c.take<Select64State>(1);
-    AM_REQUIRE(c.ok(), AM_ERR_WORKSPACE, "workspace too small: need %zu bytes (am_pairwise_select_f64_workspace_bytes), have %zu", c.off,
+    const SelectWs w = select_carve(ws, ws_bytes, N);
+    AM_REQUIRE(w.ok, AM_ERR_WORKSPACE, "workspace too small: need %zu bytes (am_pairwise_select_f64_workspace_bytes), have %zu", w.bytes,
                ws_bytes);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    AM_HIP_TRY(hipMemsetAsync(bins, 0, (size_t)KAD64_PASSES * KAD64_BINS * sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(kad64_norms_kernel, dim3((unsigned)ceil_div(N, 4)), dim3(256), 0, st, X, N, ld, D, norm);
+    AM_HIP_TRY(hipMemsetAsync(w.bins, 0, (size_t)KAD_PASSES * KAD_BINS * sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(kad64_norms_kernel, dim3((unsigned)ceil_div(N, 4)), dim3(256), 0, st, X, N, ld, D, w.norm);
     AM_LAUNCH_CHECK();
     const int64_t T = ceil_div(N, FT);
     const int chunk = kad_chunk(T * (T + 1) / 2, T);
-    int rc = launch_select64_pass<0>(X, N, ld, D, norm, chunk, state, bins, (unsigned long long)rank, out_d2, st);
-    if (rc == AM_OK) rc = launch_select64_pass<1>(X, N, ld, D, norm, chunk, state, bins, 0ull, out_d2, st);
-    if (rc == AM_OK) rc = launch_select64_pass<2>(X, N, ld, D, norm, chunk, state, bins, 0ull, out_d2, st);
+    int rc = launch_select64_pass<0>(X, N, ld, D, w.norm, chunk, w.state, w.bins, (unsigned long long)rank, out_d2, st);
+    if (rc == AM_OK) rc = launch_select64_pass<1>(X, N, ld, D, w.norm, chunk, w.state, w.bins, 0ull, out_d2, st);
+    if (rc == AM_OK) rc = launch_select64_pass<2>(X, N, ld, D, w.norm, chunk, w.state, w.bins, 0ull, out_d2, st);
     return rc;
 }
 
 extern "C" size_t am_mmd_rbf_f64_workspace_bytes(int64_t N1, int64_t N2, int D, unsigned blocks) {
     if (N1 < 1 || N2 < 1 || D < 1 || (blocks & 7u) == 0) return 0;
-    return mmd64_carve(nullptr, 0, N1, N2, blocks & 7u, mmd64_plan(N1, N2)).bytes;
+    return mmd_carve(nullptr, 0, N1, N2, 1, blocks & 7u, mmd_plan(N1, N2, FT)).bytes;
 }
 
 extern "C" int am_mmd_rbf_f64(const double* X, int64_t N1, int64_t ldx, const double* Y, int64_t N2, int64_t ldy, int D,
@@ -557,23 +374,21 @@ extern "C" int am_mmd_rbf_f64(const double* X, int64_t N1, int64_t ldx, const do
                (long long)N1, (long long)N2);
     AM_REQUIRE(ldx >= D && ldy >= D, AM_ERR_BAD_ARG, "ld < D (ldx=%lld ldy=%lld D=%d)", (long long)ldx, (long long)ldy, D);
     AM_REQUIRE(bw2_dev != nullptr || gamma >= 0.0, AM_ERR_BAD_ARG, "gamma must be >= 0 (or bw2_dev given)");
-    const Mmd64Plan plan = mmd64_plan(N1, N2);
-    const Mmd64Ws w = mmd64_carve(ws, ws_bytes, N1, N2, blocks, plan);
+    const MmdPlan plan = mmd_plan(N1, N2, FT);
+    const MmdWs w = mmd_carve(ws, ws_bytes, N1, N2, 1, blocks, plan);
     AM_REQUIRE(w.ok, AM_ERR_WORKSPACE, "workspace too small: need %zu bytes (am_mmd_rbf_f64_workspace_bytes), have %zu", w.bytes, ws_bytes);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (w.n1) hipLaunchKernelGGL(kad64_norms_kernel, dim3((unsigned)ceil_div(N1, 4)), dim3(256), 0, st, X, N1, ldx, D, w.n1);
-    if (w.n2) hipLaunchKernelGGL(kad64_norms_kernel, dim3((unsigned)ceil_div(N2, 4)), dim3(256), 0, st, Y, N2, ldy, D, w.n2);
+    if (w.n.n1) hipLaunchKernelGGL(kad64_norms_kernel, dim3((unsigned)ceil_div(N1, 4)), dim3(256), 0, st, X, N1, ldx, D, w.n.n1);
+    if (w.n.n2) hipLaunchKernelGGL(kad64_norms_kernel, dim3((unsigned)ceil_div(N2, 4)), dim3(256), 0, st, Y, N2, ldy, D, w.n.n2);
     AM_LAUNCH_CHECK();
     for (int b = 0; b < 3; ++b) {
         if (!(blocks & (1u << b))) continue;
         const bool q_is_y = b == 1, p_is_x = b == 0;
         hipLaunchKernelGGL(kad64_mmd_kernel, plan.grid[b], dim3(FTHREADS), 0, st, q_is_y ? Y : X, q_is_y ? N2 : N1, q_is_y ? ldy : ldx,
-                           (const double*)(q_is_y ? w.n2 : w.n1), p_is_x ? X : Y, p_is_x ? N1 : N2, p_is_x ? ldx : ldy,
-                           (const double*)(p_is_x ? w.n1 : w.n2), D, b < 2 ? 1 : 0, plan.chunk[b], bw2_dev, gamma, w.partial[b]);
+                           (const double*)(q_is_y ? w.n.n2 : w.n.n1), p_is_x ? X : Y, p_is_x ? N1 : N2, p_is_x ? ldx : ldy,
+                           (const double*)(p_is_x ? w.n.n1 : w.n.n2), D, b < 2 ? 1 : 0, plan.chunk[b], bw2_dev, gamma, w.partial[b]);
         AM_LAUNCH_CHECK();
-        hipLaunchKernelGGL(kad64_reduce_kernel, dim3(1), dim3(256), 0, st, (const double*)w.partial[b], (int64_t)plan.slots[b],
-                           out_sums + b);
-        AM_LAUNCH_CHECK();
+        AM_TRY(launch_mmd_reduce(w.partial[b], (int64_t)plan.slots[b], 1, out_sums + b, st));
     }
     return AM_OK;
 }
@@ -605,17 +420,9 @@ extern "C" int am_mmd_rbf_groups_f64(const double* X, int64_t N1, int64_t ldx, c
     Groups64Ws w;
     AM_REQUIRE(groups64_carve(c, n_total, B, N2, plan, w), AM_ERR_WORKSPACE,
                "workspace too small: need %zu bytes (am_mmd_rbf_groups_f64_workspace_bytes), have %zu", c.off, ws_bytes);
-    // the longest Q range of a P tile in the within pass: first tile of its first group .. last tile of its last group
-    int64_t span = 1;
-    for (int64_t t = 0, g0 = 0, g1 = 0; t < plan.TP; ++t) {
-        const int64_t pfirst = t * FT, plast = std::min<int64_t>(pfirst + FT, n_total) - 1;
-        while (offsets[g0 + 1] <= pfirst) ++g0;
-        g1 = std::max(g1, g0);
-        while (offsets[g1 + 1] <= plast) ++g1;
-        span = std::max<int64_t>(span, (offsets[g1 + 1] - 1) / FT - offsets[g0] / FT + 1);
-    }
-    const int chunk_w = (int)std::max<int64_t>(KAD_MAX_CHUNK, ceil_div(span, KADG64_WITHIN_CHUNKS));
-    const int nch_w = (int)ceil_div(span, chunk_w);      // <= min(TP, KADG64_WITHIN_CHUNKS)
+    const int64_t span = kadg_within_span(offsets, plan.TP, n_total, FT);
+    const int chunk_w = kadg_within_chunk(span);
+    const int nch_w = (int)ceil_div(span, chunk_w);      // <= min(TP, KADG_WITHIN_CHUNKS)
     hipStream_t st = static_cast<hipStream_t>(stream);
     AM_TRY(upload_group_head(w.head, offsets, B, st));
     const int64_t* offs = w.head.offs;
@@ -633,10 +440,6 @@ extern "C" int am_mmd_rbf_groups_f64(const double* X, int64_t N1, int64_t ldx, c
                        (const double*)w.yn, D, chunk_w, bw2_dev, gamma, w.pw);
     AM_LAUNCH_CHECK();
     double* rows = out_rows ? out_rows : w.rows;
-    hipLaunchKernelGGL(kadg64_rowsum_kernel, dim3((unsigned)ceil_div(n_total, 256)), dim3(256), 0, st, (const double*)w.pw, nch_w,
-                       (const double*)w.pc, plan.nch_c, plan.n_pad, n_total, rows);
-    AM_LAUNCH_CHECK();
-    hipLaunchKernelGGL(kadg64_finish_kernel, dim3((unsigned)B), dim3(256), 0, st, (const double*)rows, offs, out_groups);
-    AM_LAUNCH_CHECK();
-    return AM_OK;
+    AM_TRY(launch_kadg_rowsum(w.pw, nch_w, w.pc, plan.nch_c, plan.n_pad, n_total, rows, st));
+    return launch_kadg_finish(rows, offs, B, out_groups, st);
 }

@@ -18,10 +18,11 @@
 //                       from the tile of the first position of its first group to the tile of the last position of its
 //                       last group, masked by gid[q] == gid[p] && q != p).  A workgroup owns one P tile and a chunk of
 //                       consecutive Q tiles; a lane keeps one f64 running sum per P row it holds (LaneInfo::NT), and at the
-//                       end the sums are combined in a fixed order - the two halves of a wave (lane ^ 32), then the two wm
-//                       waves through LDS - and written to partial[chunk][position].  No atomics.
+//                       end the sums are combined in a fixed order (fold_p_rows: the two halves of a wave, lane ^ 32, then
+//                       the two wm waves through LDS) and written to partial[chunk][position].  No atomics.
 //   kadg_rowsum_kernel  per position: its chunks added in chunk order -> rows[p] = {w_p, c_p}
 //   kadg_finish_kernel  one workgroup per group: strided per-thread sums, then a tree -> out_groups[b] = {Sxx_b, Sxy_b}
+//                       (both serve am_mmd_rbf_groups_f64 too, through their launchers in kad_common.h)
 // The result depends on the list order and on nothing about where the rows are stored; two calls give the same bits.
 #include "am_common.h"
 #include "groups_common.h"
@@ -33,20 +34,6 @@ namespace am {
 
 constexpr unsigned KADG_HOLE = 0xffffffffu;          // voffset past every descriptor: the load returns 0
 constexpr size_t KADG_LDS_BYTES = ENGINE_LDS_FLOATS * sizeof(float);      // 73 728 B: two workgroups per CU
-constexpr int KADG_WITHIN_CHUNKS = 4;                // most Q chunks of a P tile in the within pass
-constexpr int64_t KADG_CROSS_CHUNKS = 64;            // most Q chunks of the cross pass once there are many P tiles ...
-constexpr int64_t KADG_CROSS_SLOTS = 4096;           // ... (P tiles) x (chunks) may reach this with few P tiles
-
-// first group whose end lies past position p (offs: B + 1 entries, offs[0] = 0 <= p < offs[B])
-__device__ __forceinline__ int kadg_group_of(const int64_t* __restrict__ offs, int B, int64_t p) {
-    int lo = 0, hi = B - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (offs[mid + 1] > p) hi = mid;
-        else lo = mid + 1;
-    }
-    return lo;
-}
 
 // one wave per list position (padding included)
 __global__ void __launch_bounds__(256) kadg_prep_kernel(const float* __restrict__ X, int64_t N1, int64_t ld, int D,
@@ -81,7 +68,7 @@ __global__ void __launch_bounds__(256) kadg_prep_kernel(const float* __restrict_
         if (!ok) atomicMax(flag, (unsigned long long)p + 1ull);
         rowoff[p] = ok ? (unsigned)(row * ld * 4) : KADG_HOLE;      // N1 * ld * 4 < 4 GiB
         norm[p] = acc;
-        gid[p] = kadg_group_of(offs, B, p);
+        gid[p] = group_of(offs, B, p);
     }
 }
 
@@ -204,17 +191,7 @@ kadg_rows_kernel(const float* __restrict__ X, int64_t N1, int64_t ldx, const uns
         };
         addr_pipeline_early<EV_DEFAULT, KTAIL>(qaddr, pa, ntiles, D, 0, lds, L, epi);
     }
-    // the two halves of a wave hold the same P rows against different Q rows; then the two wm waves, through LDS
-    double v[LaneInfo::NT];
-#pragma unroll
-    for (int nt = 0; nt < LaneInfo::NT; ++nt) v[nt] = epi.sum[nt] + __shfl_xor(epi.sum[nt], 32);
-    double* red = reinterpret_cast<double*>(lds);          // staging slabs are idle after the pipeline's last barrier
-    if (L.h == 0) {
-#pragma unroll
-        for (int nt = 0; nt < LaneInfo::NT; ++nt) red[L.wm * TB + L.wn * 64 + nt * 32 + L.r] = v[nt];
-    }
-    __syncthreads();
-    if (L.tid < TB) out[L.tid] = red[L.tid] + red[TB + L.tid];
+    fold_p_rows(epi.sum, reinterpret_cast<double*>(lds), L, out);          // staging slabs are idle after the pipeline's last barrier
 }
 
 // rows[p] = {w_p, c_p}: a position's chunks in chunk order
@@ -258,6 +235,18 @@ __global__ void __launch_bounds__(256) kadg_finish_kernel(const double* __restri
 }
 
 // ---------------------------------------------------------------- host side
+int launch_kadg_rowsum(const double* pw, int nw, const double* pc, int nc, int64_t n_pad, int64_t n_total, double* rows, hipStream_t st) {
+    hipLaunchKernelGGL(kadg_rowsum_kernel, dim3((unsigned)ceil_div(n_total, 256)), dim3(256), 0, st, pw, nw, pc, nc, n_pad, n_total, rows);
+    AM_LAUNCH_CHECK();
+    return AM_OK;
+}
+
+int launch_kadg_finish(const double* rows, const int64_t* offs, int B, double* out, hipStream_t st) {
+    hipLaunchKernelGGL(kadg_finish_kernel, dim3((unsigned)B), dim3(256), 0, st, rows, offs, out);
+    AM_LAUNCH_CHECK();
+    return AM_OK;
+}
+
 struct GroupsPlan {
     int64_t TP, TQ, n_pad;
     int chunk_c, nch_c;          // cross pass
@@ -269,9 +258,7 @@ static GroupsPlan groups_plan(int64_t n_total, int64_t N2) {
     p.TP = ceil_div(n_total, TB);
     p.TQ = ceil_div(N2, TB);
     p.n_pad = p.TP * TB;
-    // per-ROW partials: 128 doubles per (P tile, chunk), so the number of chunks is capped where kad.hip's is not
-    const int64_t cap = std::max<int64_t>(KADG_CROSS_CHUNKS, KADG_CROSS_SLOTS / p.TP);
-    p.chunk_c = (int)std::max<int64_t>(kad_chunk(p.TP * p.TQ, p.TQ), ceil_div(p.TQ, cap));
+    p.chunk_c = kadg_cross_chunk(p.TP, p.TQ);            // 128 doubles per (P tile, chunk)
     p.nch_c = (int)ceil_div(p.TQ, p.chunk_c);
     p.slots_c = (size_t)std::min<int64_t>(p.TP * p.TQ, std::max<int64_t>(KADG_CROSS_CHUNKS * p.TP, KADG_CROSS_SLOTS));
     return p;
@@ -328,16 +315,8 @@ extern "C" int am_mmd_rbf_groups_f32(const float* X, int64_t N1, int64_t ldx, co
     GroupsWs w;
     AM_REQUIRE(groups_carve(c, n_total, B, N2, plan, w), AM_ERR_WORKSPACE,
                "workspace too small: need %zu bytes (am_mmd_rbf_groups_workspace_bytes), have %zu", c.off, ws_bytes);
-    // the longest Q range of a P tile in the within pass: first tile of its first group .. last tile of its last group
-    int64_t span = 1;
-    for (int64_t t = 0, g0 = 0, g1 = 0; t < plan.TP; ++t) {
-        const int64_t pfirst = t * TB, plast = std::min<int64_t>(pfirst + TB, n_total) - 1;
-        while (offsets[g0 + 1] <= pfirst) ++g0;
-        g1 = std::max(g1, g0);
-        while (offsets[g1 + 1] <= plast) ++g1;
-        span = std::max<int64_t>(span, (offsets[g1 + 1] - 1) / TB - offsets[g0] / TB + 1);
-    }
-    const int chunk_w = (int)std::max<int64_t>(KAD_MAX_CHUNK, ceil_div(span, KADG_WITHIN_CHUNKS));
+    const int64_t span = kadg_within_span(offsets, plan.TP, n_total, TB);
+    const int chunk_w = kadg_within_chunk(span);
     const int nch_w = (int)ceil_div(span, chunk_w);      // <= min(TP, KADG_WITHIN_CHUNKS)
     hipStream_t st = static_cast<hipStream_t>(stream);
     AM_TRY(upload_group_head(w.head, offsets, B, st));
@@ -364,10 +343,6 @@ extern "C" int am_mmd_rbf_groups_f32(const float* X, int64_t N1, int64_t ldx, co
                        : launch(&kadg_rows_kernel<false, false>, &kadg_rows_kernel<true, false>);
     if (rc != AM_OK) return rc;
     double* rows = out_rows ? out_rows : w.rows;
-    hipLaunchKernelGGL(kadg_rowsum_kernel, dim3((unsigned)ceil_div(n_total, 256)), dim3(256), 0, st, (const double*)w.pw, nch_w,
-                       (const double*)w.pc, plan.nch_c, plan.n_pad, n_total, rows);
-    AM_LAUNCH_CHECK();
-    hipLaunchKernelGGL(kadg_finish_kernel, dim3((unsigned)B), dim3(256), 0, st, (const double*)rows, offs, out_groups);
-    AM_LAUNCH_CHECK();
-    return AM_OK;
+    AM_TRY(launch_kadg_rowsum(w.pw, nch_w, w.pc, plan.nch_c, plan.n_pad, n_total, rows, st));
+    return launch_kadg_finish(rows, offs, B, out_groups, st);
 }

@@ -6,17 +6,17 @@
 //   Laplacian  exp(-sqrt(d2) h_s),  h_s = 1 / (c_s sqrt(bw2))
 //   energy     -sqrt(d2)            (one "scale", no bandwidth: the MMD of k = -d is the energy distance)
 // with d2 = max((|a|^2 + |b|^2) - 2 dot(a, b), 0) in f64, f64 squared norms and the f32 matrix-core dot product - the
-// arithmetic, tile engine, grid plan and summation order of kad_mmd_kernel.  Every scale keeps its own running sum, added in
-// the order MmdEpilogue adds its one: the Gaussian sums of scale c equal those of am_mmd_rbf_f32 at gamma = g bit for bit,
-// and no scale's sums depend on which other scales share the call.
+// arithmetic, tile engine, grid plan (mmd_plan), workspace carve and summation order of kad_mmd_kernel.  Every scale keeps its
+// own running sum, added in the order MmdEpilogue adds its one: the Gaussian sums of scale c equal those of am_mmd_rbf_f32 at
+// gamma = g bit for bit, and no scale's sums depend on which other scales share the call.
 //
 // Padded rows: the Gaussian and Laplacian kernels give them a norm of +inf, exp(-inf) = 0 exactly.  The energy kernel would
 // add -inf, so it gives them a norm of 0 and drops the pair by index.
 //
-// Registers (two workgroups of four waves per CU, 256 per lane, 64 of them accumulators): one to four Gaussian scales take
-// 236 / 245 / 249 / 254, one to four Laplacian scales 240 / 249 / 255 / 256, the energy kernel 208, none with scratch memory
-// (tests/test_mmd_multi_cpu.py).  Four Laplacian scales fill the file - hence AM_MMD_MULTI_MAX = 4; a longer grid is several
-// calls.
+// Registers (two workgroups of four waves per CU, 256 per lane, 64 of them accumulators), without / with the inner-dimension
+// tail: one to four Gaussian scales take 234 / 236, 244 / 245, 248 / 249, 252 / 254; one to four Laplacian scales 240, 249,
+// 255, 256 either way; the energy kernel 206 / 208; none with scratch memory (tests/test_mmd_multi_cpu.py).  Four Laplacian
+// scales fill the file - hence AM_MMD_MULTI_MAX = 4; a longer grid is several calls.
 #include "am_common.h"
 #include "kad_common.h"
 #include "pairwise_common.h"
@@ -142,8 +142,8 @@ mmd_multi_kernel(const float* __restrict__ Q, int64_t nq, int64_t ldq, const dou
     }
 }
 
-// out[j] = sum of partial[j * count .. (j + 1) * count) for workgroup j, in the fixed order of kad_reduce_kernel: strided
-// per-thread sums, then a tree
+// out[j] = sum of partial[j * count .. (j + 1) * count) for workgroup j, in a fixed order: strided per-thread sums, then a
+// tree.  The one reduce kernel of the family (launch_mmd_reduce): am_mmd_rbf_f32 and am_mmd_rbf_f64 use it with one output.
 __global__ void __launch_bounds__(256) mmd_multi_reduce_kernel(const double* __restrict__ partial, int64_t count,
                                                                double* __restrict__ out) {
     __shared__ double red[256];
@@ -160,22 +160,10 @@ __global__ void __launch_bounds__(256) mmd_multi_reduce_kernel(const double* __r
     if (tid == 0) out[blockIdx.x] = red[0];
 }
 
-struct MultiWs {
-    double *n1, *n2, *partial[3];
-    size_t bytes;
-    bool ok;
-};
-
-static MultiWs multi_carve(void* ws, size_t ws_bytes, int64_t N1, int64_t N2, int nscales, unsigned blocks, const MmdPlan& plan) {
-    Carver c(ws, ws_bytes);
-    MultiWs w{};
-    if (blocks & (AM_MMD_XX | AM_MMD_XY)) w.n1 = c.take<double>((size_t)N1);
-    if (blocks & (AM_MMD_YY | AM_MMD_XY)) w.n2 = c.take<double>((size_t)N2);
-    for (int b = 0; b < 3; ++b)
-        if (blocks & (1u << b)) w.partial[b] = c.take<double>(plan.slots[b] * (size_t)nscales);
-    w.bytes = c.off;
-    w.ok = c.ok();
-    return w;
+int launch_mmd_reduce(const double* partial, int64_t count, int nout, double* out, hipStream_t st) {
+    hipLaunchKernelGGL(mmd_multi_reduce_kernel, dim3((unsigned)nout), dim3(256), 0, st, partial, count, out);
+    AM_LAUNCH_CHECK();
+    return AM_OK;
 }
 
 struct MultiCall {
@@ -189,7 +177,7 @@ struct MultiCall {
     unsigned blocks;
     double* out_sums;
     MmdPlan plan;
-    MultiWs w;
+    MmdWs w;
     hipStream_t st;
 };
 
@@ -201,13 +189,12 @@ static int launch_blocks(const MultiCall& c) {
         if (!(c.blocks & (1u << b))) continue;
         const bool q_is_y = b == 1, p_is_x = b == 0;
         hipLaunchKernelGGL(kernel, c.plan.grid[b], dim3(ENGINE_THREADS), MMD_MULTI_LDS_BYTES, c.st,
-                           q_is_y ? c.Y : c.X, q_is_y ? c.N2 : c.N1, q_is_y ? c.ldy : c.ldx, (const double*)(q_is_y ? c.w.n2 : c.w.n1),
-                           p_is_x ? c.X : c.Y, p_is_x ? c.N1 : c.N2, p_is_x ? c.ldx : c.ldy, (const double*)(p_is_x ? c.w.n1 : c.w.n2),
+                           q_is_y ? c.Y : c.X, q_is_y ? c.N2 : c.N1, q_is_y ? c.ldy : c.ldx, (const double*)(q_is_y ? c.w.n.n2 : c.w.n.n1),
+                           p_is_x ? c.X : c.Y, p_is_x ? c.N1 : c.N2, p_is_x ? c.ldx : c.ldy, (const double*)(p_is_x ? c.w.n.n1 : c.w.n.n2),
                            c.D, b < 2 ? 1 : 0, c.plan.chunk[b], c.bw2_dev, c.bw2, c.sc, c.w.partial[b], (int64_t)c.plan.slots[b]);
         AM_LAUNCH_CHECK();
-        hipLaunchKernelGGL(mmd_multi_reduce_kernel, dim3((unsigned)S), dim3(256), 0, c.st, (const double*)c.w.partial[b],
-                           (int64_t)c.plan.slots[b], c.out_sums + (size_t)b * S);
-        AM_LAUNCH_CHECK();
+        const int rc = launch_mmd_reduce(c.w.partial[b], (int64_t)c.plan.slots[b], S, c.out_sums + (size_t)b * S, c.st);
+        if (rc != AM_OK) return rc;
     }
     return AM_OK;
 }
@@ -229,32 +216,40 @@ static int launch_scales(const MultiCall& c) {
 
 static bool finite_positive(double v) { return v > 0.0 && v < (double)INFINITY; }
 
+// the part of a call every kernel shares: plan and workspace (`query` names the caller's own size query), then the norms
+static int open_call(MultiCall& c, const float* X, int64_t N1, int64_t ldx, const float* Y, int64_t N2, int64_t ldy, int D, int nscales,
+                     unsigned blocks, double* out_sums, void* ws, size_t ws_bytes, const char* query, am_stream_t stream) {
+    c.plan = mmd_plan(N1, N2, TB);
+    c.w = mmd_carve(ws, ws_bytes, N1, N2, nscales, blocks, c.plan);
+    AM_REQUIRE(c.w.ok, AM_ERR_WORKSPACE, "workspace too small: need %zu bytes (%s), have %zu", c.w.bytes, query, ws_bytes);
+    c.X = X, c.Y = Y, c.N1 = N1, c.N2 = N2, c.ldx = ldx, c.ldy = ldy, c.D = D;
+    c.nscales = nscales, c.blocks = blocks, c.out_sums = out_sums;
+    c.st = static_cast<hipStream_t>(stream);
+    return launch_set_norms(X, N1, ldx, Y, N2, ldy, D, c.w.n, c.st);
+}
+
 }  // namespace am
 
 using namespace am;
 
 extern "C" size_t am_mmd_multi_workspace_bytes(int64_t N1, int64_t N2, int D, int nscales, unsigned blocks) {
     if (N1 < 1 || N2 < 1 || D < 1 || nscales < 1 || nscales > AM_MMD_MULTI_MAX || (blocks & 7u) == 0) return 0;
-    return multi_carve(nullptr, 0, N1, N2, nscales, blocks & 7u, mmd_plan(N1, N2)).bytes;
+    return mmd_carve(nullptr, 0, N1, N2, nscales, blocks & 7u, mmd_plan(N1, N2, TB)).bytes;
 }
 
 extern "C" int am_mmd_multi_f32(const float* X, int64_t N1, int64_t ldx, const float* Y, int64_t N2, int64_t ldy, int D, int kernel,
                                 const float* bw2_dev, double bw2, const double* scales, int nscales, unsigned blocks,
                                 double* out_sums, void* ws, size_t ws_bytes, am_stream_t stream) {
-    AM_REQUIRE(X && Y && out_sums && scales, AM_ERR_BAD_ARG, "null pointer");
-    AM_REQUIRE(blocks != 0 && (blocks & ~7u) == 0, AM_ERR_BAD_ARG, "blocks = %u is not a mask of AM_MMD_XX | AM_MMD_YY | AM_MMD_XY", blocks);
+    AM_REQUIRE(out_sums && scales, AM_ERR_BAD_ARG, "null pointer");
     AM_REQUIRE(kernel == AM_MMD_GAUSSIAN || kernel == AM_MMD_LAPLACIAN || kernel == AM_MMD_ENERGY, AM_ERR_BAD_ARG,
                "kernel = %d is not one of AM_MMD_GAUSSIAN, AM_MMD_LAPLACIAN, AM_MMD_ENERGY", kernel);
-    AM_REQUIRE(N1 >= 1 && N2 >= 1 && D >= 1, AM_ERR_BAD_SHAPE, "N1=%lld N2=%lld D=%d", (long long)N1, (long long)N2, D);
+    int rc = check_two_sets_f32(X, N1, ldx, Y, N2, ldy, D, blocks);
+    if (rc != AM_OK) return rc;
     AM_REQUIRE(nscales >= 1 && nscales <= AM_MMD_MULTI_MAX, AM_ERR_BAD_SHAPE,
                "nscales = %d: one call takes 1 .. AM_MMD_MULTI_MAX = %d scales (split a longer grid into several calls)", nscales,
                AM_MMD_MULTI_MAX);
     AM_REQUIRE(kernel != AM_MMD_ENERGY || nscales == 1, AM_ERR_BAD_SHAPE, "nscales = %d: the energy kernel has no scale, nscales must be 1",
                nscales);
-    AM_REQUIRE(aligned16(X) && aligned16(Y) && ldx % 4 == 0 && ldy % 4 == 0 && ldx >= D && ldy >= D, AM_ERR_BAD_ARG,
-               "X/Y must be 16-byte aligned with ld %% 4 == 0 and ld >= D");
-    AM_REQUIRE(!kad_too_large(N1, ldx) && !kad_too_large(N2, ldy), AM_ERR_BAD_SHAPE,
-               "N * ld * 4 bytes of a set >= 4 GiB: one buffer descriptor spans a matrix");
     MultiCall c{};
     for (int j = 0; j < nscales; ++j) {
         AM_REQUIRE(finite_positive(scales[j]), AM_ERR_BAD_ARG, "scales[%d] = %g must be finite and positive", j, scales[j]);
@@ -262,17 +257,9 @@ extern "C" int am_mmd_multi_f32(const float* X, int64_t N1, int64_t ldx, const f
     }
     AM_REQUIRE(kernel == AM_MMD_ENERGY || bw2_dev != nullptr || finite_positive(bw2), AM_ERR_BAD_ARG,
                "bw2 = %g must be finite and positive (or bw2_dev given)", bw2);
-    c.plan = mmd_plan(N1, N2);
-    c.w = multi_carve(ws, ws_bytes, N1, N2, nscales, blocks, c.plan);
-    AM_REQUIRE(c.w.ok, AM_ERR_WORKSPACE, "workspace too small: need %zu bytes (am_mmd_multi_workspace_bytes), have %zu", c.w.bytes,
-               ws_bytes);
-    c.X = X, c.Y = Y, c.N1 = N1, c.N2 = N2, c.ldx = ldx, c.ldy = ldy, c.D = D;
     c.bw2_dev = kernel == AM_MMD_ENERGY ? nullptr : bw2_dev;
     c.bw2 = kernel == AM_MMD_ENERGY ? 1.0 : bw2;
-    c.nscales = nscales, c.blocks = blocks, c.out_sums = out_sums;
-    c.st = static_cast<hipStream_t>(stream);
-    int rc = c.w.n1 ? launch_kad_norms(X, ldx, D, N1, c.w.n1, c.st) : AM_OK;
-    if (rc == AM_OK && c.w.n2) rc = launch_kad_norms(Y, ldy, D, N2, c.w.n2, c.st);
+    rc = open_call(c, X, N1, ldx, Y, N2, ldy, D, nscales, blocks, out_sums, ws, ws_bytes, "am_mmd_multi_workspace_bytes", stream);
     if (rc != AM_OK) return rc;
     switch (kernel) {
         case AM_MMD_GAUSSIAN: return launch_scales<AM_MMD_GAUSSIAN>(c);

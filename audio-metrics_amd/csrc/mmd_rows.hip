@@ -9,7 +9,7 @@
 //
 // Every 128 x 128 tile is computed once and summed along BOTH axes of the accumulator:
 //   P rows (lane axis)      one f64 running sum per P row and lane over the Q tiles of the workgroup (RowEpilogue of
-//                           kad_groups.hip); at the end the two halves of a wave, then the two wm waves through LDS
+//                           kad_groups.hip); at the end fold_p_rows: the two halves of a wave, then the two wm waves through LDS
 //                           -> pp[chunk][band slot][128]
 //   Q rows (register axis)  per tile a lane holds 32 Q rows.  Their sums over the wave's 64 P rows are formed by a
 //                           progressive butterfly: the values of the two nt sub-tiles are added in the lane, and every
@@ -124,17 +124,8 @@ mmd_rows_kernel(const float* __restrict__ Q, int64_t nq, int64_t ldq, const doub
         epi.pnorm[nt] = p < np ? pn[p] : INFINITY;
     }
     dense_pipeline_early<EV_DEFAULT, KTAIL>(Q, nq, ldq, LinearTiles{q0}, P, np, ldp, (int64_t)tp * TB, ntiles, D, lds, L, epi);
-    // the two halves of a wave hold the same P rows against different Q rows; then the two wm waves, through LDS
-    double v[LaneInfo::NT];
-#pragma unroll
-    for (int nt = 0; nt < LaneInfo::NT; ++nt) v[nt] = epi.sum[nt] + __shfl_xor(epi.sum[nt], 32);
-    double* red = reinterpret_cast<double*>(lds);          // staging slabs are idle after the pipeline's last barrier
-    if (L.h == 0) {
-#pragma unroll
-        for (int nt = 0; nt < LaneInfo::NT; ++nt) red[L.wm * TB + L.wn * 64 + nt * 32 + L.r] = v[nt];
-    }
-    __syncthreads();
-    if (L.tid < TB) pp[((int64_t)blockIdx.y * ROWS_BAND + blockIdx.x) * TB + L.tid] = red[L.tid] + red[TB + L.tid];
+    // (staging slabs are idle after the pipeline's last barrier)
+    fold_p_rows(epi.sum, reinterpret_cast<double*>(lds), L, pp + ((int64_t)blockIdx.y * ROWS_BAND + blockIdx.x) * TB);
 }
 
 // pside[p] for the rows of the band's `ntp` P tiles: the tile's chunks in chunk order
@@ -204,7 +195,8 @@ static RowsBlock rows_block(int b, int64_t N1, int64_t N2) {
 }
 
 struct RowsWs {
-    double *n1, *n2, *pp, *qp, *pside, *run;
+    SetNorms n;
+    double *pp, *qp, *pside, *run;
     size_t bytes;
     bool ok;
 };
@@ -213,8 +205,7 @@ struct RowsWs {
 static RowsWs rows_carve(void* ws, size_t ws_bytes, int64_t N1, int64_t N2, unsigned blocks) {
     Carver c(ws, ws_bytes);
     RowsWs w{};
-    if (blocks & (AM_MMD_XX | AM_MMD_XY)) w.n1 = c.take<double>((size_t)N1);
-    if (blocks & (AM_MMD_YY | AM_MMD_XY)) w.n2 = c.take<double>((size_t)N2);
+    w.n = carve_set_norms(c, N1, N2, blocks);
     size_t pp = 0, qp = 0, rows_p = 0, rows_q = 0;
     for (int b = 0; b < 3; ++b) {
         if (!(blocks & (1u << b))) continue;
@@ -276,33 +267,26 @@ extern "C" size_t am_mmd_rbf_rows_workspace_bytes(int64_t N1, int64_t N2, int D,
 extern "C" int am_mmd_rbf_rows_f32(const float* X, int64_t N1, int64_t ldx, const float* Y, int64_t N2, int64_t ldy, int D,
                                    const float* bw2_dev, double gamma, unsigned blocks, double* out_x, double* out_y, void* ws,
                                    size_t ws_bytes, am_stream_t stream) {
-    AM_REQUIRE(X && Y, AM_ERR_BAD_ARG, "null pointer");
-    AM_REQUIRE(blocks != 0 && (blocks & ~7u) == 0, AM_ERR_BAD_ARG, "blocks = %u is not a mask of AM_MMD_XX | AM_MMD_YY | AM_MMD_XY", blocks);
     AM_REQUIRE(out_x || !(blocks & (AM_MMD_XX | AM_MMD_XY)), AM_ERR_BAD_ARG, "null pointer: out_x is written by AM_MMD_XX and AM_MMD_XY");
     AM_REQUIRE(out_y || !(blocks & (AM_MMD_YY | AM_MMD_XY)), AM_ERR_BAD_ARG, "null pointer: out_y is written by AM_MMD_YY and AM_MMD_XY");
-    AM_REQUIRE(N1 >= 1 && N2 >= 1 && D >= 1, AM_ERR_BAD_SHAPE, "N1=%lld N2=%lld D=%d", (long long)N1, (long long)N2, D);
-    AM_REQUIRE(aligned16(X) && aligned16(Y) && ldx % 4 == 0 && ldy % 4 == 0 && ldx >= D && ldy >= D, AM_ERR_BAD_ARG,
-               "X/Y must be 16-byte aligned with ld %% 4 == 0 and ld >= D");
-    AM_REQUIRE(!kad_too_large(N1, ldx) && !kad_too_large(N2, ldy), AM_ERR_BAD_SHAPE,
-               "N * ld * 4 bytes of a set >= 4 GiB: one buffer descriptor spans a matrix");
+    int rc = check_two_sets_f32(X, N1, ldx, Y, N2, ldy, D, blocks);
+    if (rc != AM_OK) return rc;
     AM_REQUIRE(bw2_dev != nullptr || gamma >= 0.0, AM_ERR_BAD_ARG, "gamma must be >= 0 (or bw2_dev given)");
     const RowsWs w = rows_carve(ws, ws_bytes, N1, N2, blocks);
     AM_REQUIRE(w.ok, AM_ERR_WORKSPACE, "workspace too small: need %zu bytes (am_mmd_rbf_rows_workspace_bytes), have %zu", w.bytes,
                ws_bytes);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    int rc = AM_OK;
-    if (w.n1) rc = launch_kad_norms(X, ldx, D, N1, w.n1, st);
-    if (rc == AM_OK && w.n2) rc = launch_kad_norms(Y, ldy, D, N2, w.n2, st);
+    rc = launch_set_norms(X, N1, ldx, Y, N2, ldy, D, w.n, st);
     if (rc == AM_OK && (blocks & AM_MMD_XX)) {
-        rc = rows_sweep<true>(rows_block(0, N1, N2), X, ldx, w.n1, X, ldx, w.n1, D, bw2_dev, gamma, w, st);
+        rc = rows_sweep<true>(rows_block(0, N1, N2), X, ldx, w.n.n1, X, ldx, w.n.n1, D, bw2_dev, gamma, w, st);
         if (rc == AM_OK) rc = rows_write(w.pside, w.run, N1, out_x, st);
     }
     if (rc == AM_OK && (blocks & AM_MMD_YY)) {
-        rc = rows_sweep<true>(rows_block(1, N1, N2), Y, ldy, w.n2, Y, ldy, w.n2, D, bw2_dev, gamma, w, st);
+        rc = rows_sweep<true>(rows_block(1, N1, N2), Y, ldy, w.n.n2, Y, ldy, w.n.n2, D, bw2_dev, gamma, w, st);
         if (rc == AM_OK) rc = rows_write(w.pside, w.run, N2, out_y, st);
     }
     if (rc == AM_OK && (blocks & AM_MMD_XY)) {
-        rc = rows_sweep<false>(rows_block(2, N1, N2), Y, ldy, w.n2, X, ldx, w.n1, D, bw2_dev, gamma, w, st);
+        rc = rows_sweep<false>(rows_block(2, N1, N2), Y, ldy, w.n.n2, X, ldx, w.n.n1, D, bw2_dev, gamma, w, st);
         if (rc == AM_OK) rc = rows_write(w.pside, nullptr, N1, out_x + 1, st);
         if (rc == AM_OK) rc = rows_write(w.run, nullptr, N2, out_y + 1, st);
     }

@@ -210,8 +210,9 @@ def test_kad_f64_kernels_use_no_scratch_memory_and_fit_two_workgroups_per_cu():
     # (kernel, instances, LDS beside the stages: the norms / groups of the Q tile, the select's 2048 counters, the wave sums)
     tile_kernels = (("kad64_select_kernel", 3, 64 * 8 + 2048 * 4), ("kad64_mmd_kernel", 1, 64 * 8 + 4 * 8),
                     ("kadg64_rows_kernel", 2, 64 * 8 + 64 * 4))
-    small_kernels = (("kad64_scan_kernel", 3), ("kad64_norms_kernel", 1), ("kad64_reduce_kernel", 1), ("kadg64_prep_kernel", 1),
-                     ("kadg64_rowsum_kernel", 1), ("kadg64_finish_kernel", 1))
+    # (the scan, reduce, row-sum and finish kernels are those of the f32 forms: tests/test_kad_cpu.py, test_mmd_multi_cpu.py,
+    # test_kad_groups_cpu.py)
+    small_kernels = (("kad64_norms_kernel", 1), ("kadg64_prep_kernel", 1))
     assert sum(c for _, c, *_ in tile_kernels + small_kernels) == len(usage), sorted(usage)
     for n, u in usage.items():
         assert u["scratch"] == 0, (n, u)
