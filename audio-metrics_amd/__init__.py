@@ -16,6 +16,7 @@ from .metrics.kad import kernel_audio_distance_per_group                      # 
 from .metrics.kad_stats import kernel_audio_distance_with_error              # noqa: F401
 from .metrics.kad_stats import kernel_audio_distance_compare                  # noqa: F401
 from .metrics.kad_stats import mmd_standard_error, mmd_difference_test        # noqa: F401
+from .metrics.kad_perm import kernel_audio_distance_permutation_test, mmd_permutation_null   # noqa: F401
 from .metrics.mmd import kernel_audio_distance_multiscale, energy_distance   # noqa: F401
 from .metrics.prdc import prdc, nearest_neighbour_distances                   # noqa: F401
 from .metrics.neighbors import nearest_neighbors                              # noqa: F401

@@ -58,6 +58,9 @@ SIGNATURES = {
     "am_mmd_rbf_rows_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int, ctypes.c_uint]),
     "am_mmd_rbf_rows_f32": (c_int, [_P, c_int64, c_int64, _P, c_int64, c_int64, c_int, _P, c_double, ctypes.c_uint, _P, _P, _P,
                                     c_size_t, _P]),
+    "am_mmd_rbf_cells_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int, ctypes.c_uint]),
+    "am_mmd_rbf_cells_f32": (c_int, [_P, c_int64, c_int64, _P, c_int64, _P, c_int, _P, c_int64, c_int64, _P, c_int64, _P, c_int,
+                                     c_int, _P, c_double, ctypes.c_uint, _P, _P, _P, _P, c_size_t, _P]),
     "am_mmd_multi_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int, c_int, ctypes.c_uint]),
     "am_mmd_multi_f32": (c_int, [_P, c_int64, c_int64, _P, c_int64, c_int64, c_int, c_int, _P, c_double, _P, c_int, ctypes.c_uint,
                                  _P, _P, c_size_t, _P]),

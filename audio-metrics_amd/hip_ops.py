@@ -765,6 +765,78 @@ def mmd_rbf_row_sums(x, y, bw2=None, gamma=None, blocks=7):
     return out_x, out_y
 
 
+MMD_CELL = 32                                                        # AM_MMD_CELL: positions per cell
+
+
+def _cell_units(units, n_pos, name):
+    """(U, the ctypes int64 array of the U + 1 cell offsets or None) of one side of mmd_rbf_cell_sums"""
+    cells = (n_pos + MMD_CELL - 1) // MMD_CELL
+    if units is None:
+        return cells, None
+    offs = [int(o) for o in units]
+    u = len(offs) - 1
+    if u < 1 or offs[0] != 0 or offs[-1] != cells or any(offs[i + 1] <= offs[i] for i in range(u)):
+        raise ValueError(f"{name} must be cell offsets that start at 0, increase strictly and end at {cells} "
+                         f"(got {offs[:4]}{'...' if u > 3 else ''} ending at {offs[-1] if offs else None})")
+    return u, (ctypes.c_int64 * (u + 1))(*offs)
+
+
+def mmd_rbf_cell_sums(x, y, idx_x=None, idx_y=None, units_x=None, units_y=None, blocks=7, gamma=None, bw2=None):
+    """Unit-pair sums of the Gaussian kernel blocks in one library call (am_mmd_rbf_cells_f32): (xx [U1, U1], yy [U2, U2],
+    xy [U1, U2]), float64 device tensors, None for a block `blocks` (MMD_XX | MMD_YY | MMD_XY) does not name.  A set is a
+    list of positions - idx_x / idx_y: int64 device tensors of stored-row indices, -1 for an empty (padding) position; None:
+    the rows in stored order.  Cell a is the positions [32 a, 32 a + 32); units_x / units_y: host cell offsets (from 0 to the
+    number of cells, strictly increasing), None: every cell is a unit.  Entry [u, v] is the sum of k over the position pairs
+    of the two units, inside one set without p == q (by position).  `bw2` / `gamma` as for mmd_rbf_sums.  float32 rows only.
+    Where an index list was given the flag word of the call is read back (the one host synchronisation) and an index
+    outside [0, n) other than -1 raises ValueError; the kernels never dereference it."""
+    for t, name in ((x, "x"), (y, "y")):
+        if is_f64(t):
+            raise NotImplementedError(f"mmd_rbf_cell_sums takes float32 rows ({name} holds float64 rows; the float64 matrix-core "
+                                      "form is not implemented)")
+        if not torch.is_tensor(t) or t.dim() != 2:
+            raise ValueError(f"{name} must be a 2-D tensor, got {tuple(getattr(t, 'shape', ()))}")
+    if x.shape[1] != y.shape[1]:
+        raise ValueError(f"feature widths differ: {x.shape[1]} and {y.shape[1]}")
+    blocks = int(blocks)
+    if blocks < 1 or blocks > 7:
+        raise ValueError(f"blocks={blocks} is not a mask of MMD_XX | MMD_YY | MMD_XY")
+    bw2_arg, gamma_arg = _bandwidth_args(bw2, gamma)
+    pos = []
+    for idx, rows, name in ((idx_x, x.shape[0], "idx_x"), (idx_y, y.shape[0], "idx_y")):
+        if idx is not None and (not torch.is_tensor(idx) or idx.dim() != 1 or idx.numel() == 0 or idx.is_floating_point()):
+            raise ValueError(f"{name} must be a non-empty 1-D integer tensor of stored-row indices")
+        pos.append(int(idx.numel()) if idx is not None else int(rows))
+    (u1, host_ux), (u2, host_uy) = _cell_units(units_x, pos[0], "units_x"), _cell_units(units_y, pos[1], "units_y")
+    lib = _lib.load()
+    x, y = as_matrix(x, "x"), as_matrix(y, "y")
+    dev = _same_device(x, y)
+    idx_x, idx_y = _group_index(idx_x, pos[0], x), _group_index(idx_y, pos[1], y)
+    (n, d), m = x.shape, y.shape[0]
+    nan = float("nan")
+    xx = torch.full((u1, u1), nan, dtype=torch.float64, device=dev) if blocks & MMD_XX else None
+    yy = torch.full((u2, u2), nan, dtype=torch.float64, device=dev) if blocks & MMD_YY else None
+    xy = torch.full((u1, u2), nan, dtype=torch.float64, device=dev) if blocks & MMD_XY else None
+    nb = lib.am_mmd_rbf_cells_workspace_bytes(pos[0], pos[1], d, blocks)
+    ws = _workspace(nb, dev)
+    null = ctypes.c_void_p(None)
+    opt = lambda t: _ptr(t) if t is not None else null
+    host = lambda a: ctypes.cast(a, ctypes.c_void_p) if a is not None else null
+    _call(lib, "am_mmd_rbf_cells_f32", dev, _ptr(x), n, _ld(x), opt(idx_x), pos[0], host(host_ux), u1,
+          _ptr(y), m, _ld(y), opt(idx_y), pos[1], host(host_uy), u2, d, bw2_arg, gamma_arg, blocks, opt(xx), opt(yy), opt(xy),
+          _ptr(ws), nb)
+    if idx_x is not None or idx_y is not None:
+        flag = int(ws[:8].view(torch.int64).item())
+        if flag != 0:
+            p = flag - 1
+            found = [f"{name}[{p}] = {int(idx[p].item())} (outside [0, {rows}))" for idx, rows, name in
+                     ((idx_x, n, "idx_x"), (idx_y, m, "idx_y"))
+                     if idx is not None and p < idx.numel() and not -1 <= int(idx[p].item()) < rows]
+            raise ValueError("mmd_rbf_cell_sums: " + " / ".join(found) + ": positions are named by stored-row index, -1 marks an "
+                             "empty one")
+    return xx, yy, xy
+
+
 MMD_KERNELS = {"gaussian": 0, "laplacian": 1, "energy": 2}        # enum am_mmd_kernel
 MMD_MULTI_MAX = 4                                                    # AM_MMD_MULTI_MAX: scales per library call
 

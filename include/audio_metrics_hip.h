@@ -319,6 +319,45 @@ int am_mmd_rbf_rows_f32(const float* X, int64_t N1, int64_t ldx,
                         void* ws, size_t ws_bytes, am_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Unit-pair sums of the three Gaussian kernel blocks (csrc/mmd_cells.hip, f32 tile engine): what a permutation test of the
+ * unbiased MMD^2 is built from.  The MMD^2 of any relabelling of exchangeable units is a quadratic form in the matrix of
+ * pair sums between units, so one Gram sweep prices any number of permutations.  k, d2, gamma / bw2_dev as for am_mmd_rbf_f32.
+ *   Positions.  A set is a list of positions: position p of X is row idx_x[p] (DEVICE int64 [n1_pos]); idx_x == NULL names
+ *     the rows in stored order and then n1_pos must equal N1.  An index outside [0, N1) marks an EMPTY position: it is never
+ *     dereferenced, its squared norm counts as +inf (k = 0) and it contributes to no sum.  -1 is the padding marker; any other
+ *     out-of-range value is empty too and the FIRST 8 BYTES OF `ws` receive 1 + the largest position (in its own list) that
+ *     held one (0 = none), as am_mmd_rbf_groups_f32 reports it.  The same for Y.
+ *   Cells.  Cell a of a set is its positions [32 a, 32 a + 32); C = ceil(n_pos / 32).  The value of the cell pair (a, b) is
+ *     the sum of k(p, q) over its positions - inside one set without p == q, dropped by POSITION (duplicated rows stay each
+ *     other's pairs).  Summed in a fixed order: the 16 values of a lane in register order, then one xor tree over the 64 lanes.
+ *   Units.  units_x: HOST, U1 + 1 cell offsets, strictly increasing from 0 to C1 - unit u is the cells [units_x[u],
+ *     units_x[u + 1]) - or NULL: every cell is a unit (U1 is ignored).  With offsets the cell sums stay in the workspace and
+ *     out[u][v] is the sum of the unit pair's cells in row-major cell order, one thread per element.
+ *   out_xx DEVICE [U1][U1], out_yy DEVICE [U2][U2], out_xy DEVICE [U1][U2] doubles, dense.  `blocks` is a mask of AM_MMD_XX |
+ *     AM_MMD_YY | AM_MMD_XY; only the named outputs are written and the others may be NULL.
+ * XX and YY sweep the upper-triangular tiles and store every cell value to [a][b] and [b][a] (of a diagonal tile the cells
+ * a <= b): without unit offsets the output is exactly symmetric, one value written twice.  XY sweeps every tile once.  Both
+ * operands are gathered through 32-bit byte-offset tables, dense input included - no gathered copy is made.  Every output
+ * element is written exactly once: no partials, no atomics on floating-point data, two calls give the same bits, a block's
+ * output does not depend on the other blocks of the call, and the result depends on the position lists only, not on where
+ * the rows are stored.  A non-finite row makes exactly the cells (units) of its own cell (unit) row and column NaN.
+ * Workspace: the tables, and one cell matrix per named block (8 C^2 bytes: 78 MB at 100 000 positions) for the unit fold.
+ * X, Y, ld, alignment, any D >= 1, the 4 GiB rule: as for am_mmd_rbf_f32; 1 <= n_pos < 2^30.  A null X / Y or output of a
+ * named block, a bad mask, offsets that do not run from 0 to C, gamma < 0 without bw2_dev -> AM_ERR_BAD_ARG; bad sizes, n_pos
+ * != N without a list, an empty unit -> AM_ERR_BAD_SHAPE; AM_ERR_WORKSPACE.  Validated before the first HIP call;
+ * stream-ordered, no host synchronisation.
+ * ------------------------------------------------------------------------- */
+#define AM_MMD_CELL 32
+size_t am_mmd_rbf_cells_workspace_bytes(int64_t n1_pos, int64_t n2_pos, int D, unsigned blocks);
+int am_mmd_rbf_cells_f32(const float* X, int64_t N1, int64_t ldx, const int64_t* idx_x, int64_t n1_pos,
+                         const int64_t* units_x, int U1,      /* HOST, U1 + 1 cell offsets, or NULL: unit = cell */
+                         const float* Y, int64_t N2, int64_t ldy, const int64_t* idx_y, int64_t n2_pos,
+                         const int64_t* units_y, int U2,
+                         int D, const float* bw2_dev, double gamma, unsigned blocks,
+                         double* out_xx, double* out_yy, double* out_xy,   /* DEVICE [U1][U1], [U2][U2], [U1][U2] */
+                         void* ws, size_t ws_bytes, am_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Whole-set kernel sums under several kernels at once (csrc/mmd_multi.hip, f32 tile engine): the three sums of
  * am_mmd_rbf_f32 for up to AM_MMD_MULTI_MAX scales of one kernel family in ONE Gram pass - the tile work of a block is done
  * once and every scale is one more epilogue value on the same accumulator tile.  With d2 as above and the scales c_s:
