@@ -9,7 +9,9 @@
 //             v_mfma_f32_32x32x2_f32 in chains of FLUSH*32 rows that are then
 //             added into f64 accumulators, so rounding does not grow with N,
 //           - per-slab f64 partial tiles go to the workspace and are summed in a
-//             fixed order (deterministic, no float atomics).
+//             fixed order (deterministic, no float atomics),
+//           - D < 128 (less than one tile): the products are summed in f64 throughout
+//             (scatter_small_kernel).
 #include "am_common.h"
 #include "tile_engine.h"
 #include <algorithm>
@@ -265,6 +267,59 @@ __global__ void __launch_bounds__(256) scatter_reduce_kernel(const double* __res
     if (tp != tq) out[(int64_t)b * D + a] = s;
 }
 
+// Matrices narrower than one MFMA tile (D < TB): the same f32-centred values, but their (exact) products are summed in f64
+// from the first row on.  The 128 x 128 tile would be mostly padding at these widths, and - the reason this path exists - a
+// short diagonal does not average the rounding of the f32 chains: one chain of 32 .. 256 rows leaves 1e-7 .. 2.5e-7 on a
+// diagonal element, which is the error of the trace at D <= 5 and still 1e-7 at D = 34 (below one tile the trace does not
+// keep a factor 2 under its 1e-7 contract; from D = 127 up it measures 2e-8 .. 4e-8).  Workgroup = (row slab, pair of 32-column
+// blocks bp <= bq); thread t owns the elements (t / 32 + 8 j, t % 32), j < 4, of the 32 x 32 block (bp, bq), computes those on
+// or above the diagonal and writes both mirror images into the slab's partial tile, which scatter_reduce_kernel sums as it
+// does the MFMA kernel's (one triangle tile: D < TB).
+constexpr int SC_SMALL_BLK = 32;
+constexpr int SC_SMALL_ROWS = 64;    // rows staged in LDS per step
+__global__ void __launch_bounds__(256) scatter_small_kernel(const float* __restrict__ X, int64_t N, int64_t ld, int D,
+                                                            const double* __restrict__ mean, int64_t rows_per_slab, int npairs,
+                                                            double* __restrict__ partial) {
+    __shared__ float xa[SC_SMALL_ROWS][SC_SMALL_BLK + 1], xb[SC_SMALL_ROWS][SC_SMALL_BLK + 1];
+    const int tid = threadIdx.x;
+    const int slab = blockIdx.x / npairs;
+    int bp, bq;
+    tri_decode((int)(blockIdx.x % npairs), (D + SC_SMALL_BLK - 1) / SC_SMALL_BLK, bp, bq);
+    const int64_t r0 = (int64_t)slab * rows_per_slab;
+    const int64_t r1 = (r0 + rows_per_slab < N) ? r0 + rows_per_slab : N;
+    const int col = tid % SC_SMALL_BLK;
+    const int ca = bp * SC_SMALL_BLK + col, cb = bq * SC_SMALL_BLK + col;       // this thread's column of either strip
+    const float mua = (float)mean[ca < D ? ca : D - 1], mub = (float)mean[cb < D ? cb : D - 1];
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int64_t base = r0; base < r1; base += SC_SMALL_ROWS) {
+        for (int e = tid; e < SC_SMALL_ROWS * SC_SMALL_BLK; e += 256) {     // (e % 32 == col: 256 is a multiple of 32)
+            const int r = e / SC_SMALL_BLK;
+            const int64_t row = base + r;
+            xa[r][col] = (row < r1 && ca < D) ? X[row * ld + ca] - mua : 0.f;
+            xb[r][col] = (row < r1 && cb < D) ? X[row * ld + cb] - mub : 0.f;
+        }
+        __syncthreads();
+        const int rows = (int)((r1 - base < SC_SMALL_ROWS) ? r1 - base : SC_SMALL_ROWS);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int p = tid / SC_SMALL_BLK + 8 * j;
+            if ((bp < bq || p <= col) && bp * SC_SMALL_BLK + p < D && cb < D)
+                for (int r = 0; r < rows; ++r) acc[j] = fma((double)xa[r][p], (double)xb[r][col], acc[j]);
+        }
+        __syncthreads();
+    }
+    double* out = partial + (int64_t)slab * (TB * TB);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int p = tid / SC_SMALL_BLK + 8 * j;
+        const int gp = bp * SC_SMALL_BLK + p;
+        if ((bp < bq || p <= col) && gp < D && cb < D) {
+            out[gp * TB + cb] = acc[j];
+            out[cb * TB + gp] = acc[j];
+        }
+    }
+}
+
 __global__ void zero_f64_kernel(double* __restrict__ p, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) p[i] = 0.0;
@@ -516,7 +571,11 @@ static int run_colsum(const float* X, int64_t N, int D, int64_t ld, double scale
 
 static int run_scatter(const float* X, int64_t N, int D, int64_t ld, const double* mean, double scale, double* out,
                        double* partial, const StatsPlan& p, hipStream_t st) {
-    if (D % TB == 0)
+    if (D < TB) {                                          // (one triangle tile: p.ntri == 1)
+        const int nb = (int)ceil_div(D, SC_SMALL_BLK), npairs = nb * (nb + 1) / 2;
+        hipLaunchKernelGGL(scatter_small_kernel, dim3((unsigned)(p.nslabs * npairs)), dim3(256), 0, st, X, N, ld, D, mean, p.slab_rows,
+                           npairs, partial);
+    } else if (D % TB == 0)
         hipLaunchKernelGGL(scatter_partial_kernel<true>, dim3((unsigned)(p.ntri * p.nslabs)), dim3(ENGINE_THREADS), 0, st, X, N, ld,
                            D, mean, p.slab_rows, p.ntri, partial);
     else

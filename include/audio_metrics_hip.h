@@ -85,7 +85,8 @@ int am_scatter_f64(const double* X, int64_t N, int D, int64_t ld, const double* 
  * Subset b is the rows X[idx[offsets[b] + j]], j < n_b = offsets[b + 1] - offsets[b]; no gathered copy is made, the rows are
  * read whole through the index list, and the number of launches does not depend on B (the concatenated list is cut into
  * chunks that never straddle a subset).  Numerics contract of am_stats_f32 / am_stats_f64: f64 means; float32 rows centred
- * in f32, products on the f32 matrix cores in chains of 256 rows, f64 across; float64 rows entirely in f64.  n_b == 1 ->
+ * in f32, products on the f32 matrix cores in chains of 256 rows, f64 across (at every D: am_stats_f32 itself sums the
+ * products in f64 when D < 128); float64 rows entirely in f64.  n_b == 1 ->
  * zero covariance; n_b == 0 -> AM_ERR_BAD_SHAPE.  Indices may repeat and come in any order.
  *   idx      DEVICE, offsets[B] int64 entries        offsets  HOST, B + 1 entries, offsets[0] == 0, increasing
  *   means    DEVICE [B][D]                            covs     DEVICE [B][D][D]

@@ -400,7 +400,8 @@ def test_one_launch_add_matches_the_chain(am, d, splits):
     for got in (pushed, chained):
         np.testing.assert_allclose(got.mean.cpu().numpy(), want_mean, rtol=0, atol=1e-12)
         assert np.linalg.norm(got.cov.cpu().numpy() - want_cov) <= 3e-7 * np.linalg.norm(want_cov)
-    # the two paths differ only in how the <= 128 products of a batch entry are summed (f64 here, an f32 MFMA chain there)
+    # the two paths differ only in how the <= 128 products of a batch entry are summed (fma in row order here, the
+    # order of am_stats_f32 there: f64 as well below 128 columns, an f32 MFMA chain from 128 up)
     assert float((pushed.cov - chained.cov).norm() / chained.cov.norm()) <= 2e-7
     # stats-only sets take the same path without touching a store
     lean = am.AudioMetricsData(False)
