@@ -20,6 +20,7 @@ from .metrics.kad_perm import kernel_audio_distance_permutation_test, mmd_permut
 from .metrics.mmd import kernel_audio_distance_multiscale, energy_distance   # noqa: F401
 from .metrics.prdc import prdc, nearest_neighbour_distances                   # noqa: F401
 from .metrics.neighbors import nearest_neighbors                              # noqa: F401
+from .metrics.fidelity import sample_fidelity, sample_fidelity_per_group, fidelity_by_group   # noqa: F401
 from .metrics.mauve import kmeans, mauve_score, mauve_from_histograms         # noqa: F401
 from .metrics.apa import apa, apa_compute_d_x_xp                              # noqa: F401
 

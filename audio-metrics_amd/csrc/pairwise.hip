@@ -39,20 +39,7 @@ __global__ void __launch_bounds__(256) row_sqnorm_kernel(const float* __restrict
 }
 
 // ------------------------------------------------- radius -> squared threshold
-__device__ __forceinline__ float threshold_of_radius(float R) {
-    if (!(R > 0.f)) return 0.f;                     // R == 0 (or NaN): nothing is strictly inside
-    if (isinf(R)) return R;
-    float c = R * R;
-    for (int it = 0; it < 8; ++it) {                // walk down while the predecessor still reaches R
-        const float p = __uint_as_float(__float_as_uint(c) - 1u);
-        if (c > 0.f && sqrt_rn(p) >= R) c = p; else break;
-    }
-    for (int it = 0; it < 8; ++it) {                // walk up until sqrt_rn(c) >= R
-        if (sqrt_rn(c) < R) c = __uint_as_float(__float_as_uint(c) + 1u); else break;
-    }
-    return c;
-}
-
+// (threshold_of_radius: pairwise_common.h, shared with sample_scores.hip)
 __global__ void threshold_kernel(const float* __restrict__ R, int64_t n, float* __restrict__ T) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) T[i] = threshold_of_radius(R[i]);

@@ -73,6 +73,22 @@ static inline int check_matrix(const float* p, int64_t n, int64_t ld, int D, con
 
 __device__ __forceinline__ float sqrt_rn(float x) { return (float)sqrt((double)x); }  // correctly rounded
 
+// radius -> squared threshold:  sqrt_rn(d2) < R  <=>  d2 < T(R),  T(R) = min { t : sqrt_rn(t) >= R }   (the PRDC counts of
+// pairwise.hip and the per-sample scores of sample_scores.hip decide membership with it)
+__device__ __forceinline__ float threshold_of_radius(float R) {
+    if (!(R > 0.f)) return 0.f;                     // R == 0 (or NaN): nothing is strictly inside
+    if (isinf(R)) return R;
+    float c = R * R;
+    for (int it = 0; it < 8; ++it) {                // walk down while the predecessor still reaches R
+        const float p = __uint_as_float(__float_as_uint(c) - 1u);
+        if (c > 0.f && sqrt_rn(p) >= R) c = p; else break;
+    }
+    for (int it = 0; it < 8; ++it) {                // walk up until sqrt_rn(c) >= R
+        if (sqrt_rn(c) < R) c = __uint_as_float(__float_as_uint(c) + 1u); else break;
+    }
+    return c;
+}
+
 // |x|^2 in f32 in the fixed order the exact kernels and oracle/exact_c share (pairwise.hip)
 __global__ void row_sqnorm_kernel(const float* __restrict__ X, int64_t N, int64_t ld, int D, float* __restrict__ out);
 int launch_norms(const float* X, int64_t N, int64_t ld, int D, float* out, hipStream_t st);

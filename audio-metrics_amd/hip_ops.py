@@ -1060,6 +1060,52 @@ def knn_search_chunks(n, m, d, k):
     return int(_lib.load().am_knn_search_chunks(int(n), int(m), int(d), int(k)))
 
 
+# ---- per-sample realism, ball count and rarity on the PRDC manifold (csrc/sample_scores.hip) ----
+def sample_scores(x, y, r_y):
+    """Realism, ball count and rarity of every row of x against the rows of y and their k-NN radii r_y
+    (am_sample_scores_f32): (realism float32 [N], realism_index int64 [N], ball_count int32 [N], rarity float32 [N],
+    rarity_index int64 [N]) as device tensors, stream-ordered, nothing waits for the device.  realism = max_j r_j / |x - y_j|
+    (+inf on a row of y with a positive radius), ball_count = the balls the row lies in, with the bits of
+    prdc_counts(y, x, r_y, .)[0], rarity = the smallest radius among those balls (0 outside every ball); indices name rows
+    of y, ties go to the smallest, -1 where there is none.  A radius that is not > 0 is nobody's ball."""
+    if is_f64(x) or is_f64(y) or is_f64(r_y):
+        raise NotImplementedError("sample_scores takes float32 rows (the float64 matrix-core form is not implemented)")
+    if x.dim() != 2 or y.dim() != 2:
+        raise ValueError(f"x and y must be 2-D, got shapes {tuple(x.shape)} and {tuple(y.shape)}")
+    if x.shape[1] != y.shape[1]:
+        raise ValueError(f"feature widths differ: {x.shape[1]} and {y.shape[1]}")
+    if x.shape[0] < 1 or y.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError(f"sample_scores needs rows on both sides (got shapes {tuple(x.shape)} and {tuple(y.shape)})")
+    if not torch.is_tensor(r_y) or r_y.dim() != 1 or r_y.shape[0] != y.shape[0] or r_y.dtype != torch.float32:
+        raise ValueError(f"r_y must be a float32 tensor with one radius per row of y ({y.shape[0]}), got "
+                         f"{tuple(r_y.shape) if torch.is_tensor(r_y) else type(r_y).__name__}"
+                         f"{' ' + str(r_y.dtype) if torch.is_tensor(r_y) else ''}")
+    lib = _lib.load()
+    same = x is y
+    x = as_matrix(x, "x")
+    y = x if same else as_matrix(y, "y")
+    _require_cuda(r_y, "r_y")
+    dev = _same_device(x, y, r_y)
+    r_y = r_y.contiguous()
+    n, d = x.shape
+    m = y.shape[0]
+    realism = torch.empty(n, dtype=torch.float32, device=dev)
+    realism_idx = torch.empty(n, dtype=torch.int64, device=dev)
+    count = torch.empty(n, dtype=torch.int32, device=dev)
+    rarity = torch.empty(n, dtype=torch.float32, device=dev)
+    rarity_idx = torch.empty(n, dtype=torch.int64, device=dev)
+    nb = lib.am_sample_scores_workspace_bytes(n, m, d)
+    ws = _workspace(nb, dev)
+    _call(lib, "am_sample_scores_f32", dev, _ptr(x), n, _ld(x), _ptr(y), m, _ld(y), d, _ptr(r_y), _ptr(realism),
+          _ptr(realism_idx), _ptr(count), _ptr(rarity), _ptr(rarity_idx), _ptr(ws), nb)
+    return realism, realism_idx, count, rarity, rarity_idx
+
+
+def sample_scores_chunks(n, m, d):
+    """Column chunks the plan cuts the rows of y into (am_sample_scores_chunks; tests and tools)."""
+    return int(_lib.load().am_sample_scores_chunks(int(n), int(m), int(d)))
+
+
 # ---- k-means: the two halves of a Lloyd iteration (csrc/kmeans.hip) ----
 def _kmeans_check(what, x, c):
     if is_f64(x) or is_f64(c):

@@ -539,6 +539,35 @@ int am_kmeans_update_f32(const float* X, int64_t N, int64_t ldx, int D,
                          void* ws, size_t ws_bytes, am_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * PER-SAMPLE realism, ball count and rarity on the PRDC manifold (csrc/sample_scores.hip)   no counterpart in the reference
+ *   X: the samples (N rows), Y: the manifold set (M rows), r_y: device float[M], the k-NN radius of row j of Y (what
+ *   am_knn_radii_f32(Y, Y) returns).  One Gram pass on the exact f32 tile engine, no N x M matrix.  Per pair, all in f32:
+ *     d2      = max(fmaf(-2, <x_i, y_j>, |x_i|^2 + |y_j|^2), 0), NaN -> +inf: the bits of am_knn_search_f32(squared) and of
+ *               the exact PRDC kernel (same row norms, same inner order)
+ *     radius  one that is not > 0 (zero, negative, NaN) counts as 0: nobody's ball, ratio 0
+ *     member  d2 < T(r_j)  <=>  sqrt_rn(d2) < r_j, the strict test of am_prdc_counts_f32
+ *     ratio   q = fdiv_rn(fmul_rn(r_j, r_j), d2), correctly rounded; NaN (0 / 0, inf / inf) counts as 0; d2 == 0 with
+ *             r_j > 0 gives +inf
+ *   Outputs per row i of X, all overwritten:
+ *     out_realism[i]     = sqrt_rn(max_j q)        (Kynkaanniemi et al. 2019: max_j r_j / |x_i - y_j|; >= 1: in some ball)
+ *     out_realism_idx[i] = the j that attains it, ties to the SMALLEST j; -1 where the maximum is 0 (no row of Y with a
+ *                          positive radius at a finite distance: a non-finite sample row, all radii 0)
+ *     out_count[i]       = #{ j : member } - the bits of out_col_count of am_prdc_counts_f32(R = Y, C = X, r_ref = r_y, ..)
+ *     out_rarity[i]      = min { r_j : member }   (Han et al. 2023), out_rarity_idx[i] = the j that attains it, ties to the
+ *                          smallest j; 0.0f and -1 for a row outside every ball
+ *   No floating-point atomics: two calls return the same bits, whatever the chunking.  X may be Y (nothing is skipped:
+ *   every row then has realism +inf).  M < 2^32 - 1; X, Y as for am_knn_search_f32 (16-byte aligned, ld % 4 == 0,
+ *   ld >= D).  Workspace: the row norms, two floats per column and [am_sample_scores_chunks][N] (uint64, uint64, int32)
+ *   partials.  Everything is validated before the first HIP call; the call is asynchronous.
+ * ------------------------------------------------------------------------- */
+size_t am_sample_scores_workspace_bytes(int64_t N, int64_t M, int D);
+int am_sample_scores_chunks(int64_t N, int64_t M, int D);      /* column chunks the plan uses (tests, tools) */
+int am_sample_scores_f32(const float* X, int64_t N, int64_t ldx, const float* Y, int64_t M, int64_t ldy, int D,
+                         const float* r_y, float* out_realism, int64_t* out_realism_idx, int32_t* out_count,
+                         float* out_rarity, int64_t* out_rarity_idx,
+                         void* ws, size_t ws_bytes, am_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * A9, partitioned form for one-process-per-GPU callers that all hold the FULL set X.
  * The self-distance matrix is bitwise symmetric, so only half of the tile pairs are multiplied
  * (csrc/pairwise.hip, knn_sym_kernel); rank `part` of `nparts` owns a contiguous range of the 128-row blocks.
