@@ -234,7 +234,8 @@ __device__ __forceinline__ unsigned long long lanes_lt(float a, float b) { retur
 template <int KCAP, class Lane = LaneInfo, int TBX = TB, int MT = 2>
 struct KnnFastEpilogue {
     static constexpr int NWAVES = TBX == WIDE_TILE_ROWS ? 8 : 4;   // waves per workgroup
-    static constexpr int NT = Lane::NT;                             // 32-row P tiles per wave
+    static constexpr int NT = Lane::NT;                             // P tiles per wave
+    static constexpr int QT = Lane::QT, GS = Lane::GSTRIDE;         // Q rows of an accumulator tile, of a register group to the next
     // ACC_INIT (pstat_engine.h): the accumulators start at c0_j = |x_j|^2 / dsc (dsc = -2 / scales: c0_j = -|x_j|^2 / 2 in the
     // units of the scaled dot product), so an element holds a' = <x_i, x_j>' + c0_j and the approximate squared distance is
     // dsc a' + |x_i|^2 - a DEcreasing function of a', exact up to the scaling by a power of two.  The tests of the fast path
@@ -317,26 +318,26 @@ struct KnnFastEpilogue {
             aux[(t & 1) * 2 * TBX + TBX + L.tid] = ACC_INIT ? aux_t * idsc : aux_t;
         }
     }
-    // start value of accumulator tile mt of the half tile L.wm: register 4 g + e <-> column mt * 32 + g * 8 + h * 4 + e
+    // start value of accumulator tile mt of the unit L.wm: register 4 g + e <-> column mt * QT + g * GS + h * 4 + e
     __device__ __forceinline__ f32x16 acc_init(int t, int mt) const {
-        const float* a = aux + (t & 1) * 2 * TBX + L.wm * (MT * 32) + L.h * 4 + mt * 32;
+        const float* a = aux + (t & 1) * 2 * TBX + L.wm * (MT * QT) + L.h * 4 + mt * QT;
         f32x16 c;
 #pragma unroll
         for (int g4 = 0; g4 < 4; ++g4) {
-            const f32x4 v = *reinterpret_cast<const f32x4*>(a + g4 * 8);
+            const f32x4 v = *reinterpret_cast<const f32x4*>(a + g4 * GS);
             c[g4 * 4 + 0] = v.x; c[g4 * 4 + 1] = v.y; c[g4 * 4 + 2] = v.z; c[g4 * 4 + 3] = v.w;
         }
         return c;
     }
     __device__ __forceinline__ void finish(int t, int64_t qtile, f32x16 (&acc)[MT][NT]) {
-        const float* a = aux + (t & 1) * 2 * TBX + L.wm * (MT * 32) + L.h * 4;
+        const float* a = aux + (t & 1) * 2 * TBX + L.wm * (MT * QT) + L.h * 4;
         const bool mirror = qtile != pblock;                // the diagonal tile holds both directions itself
 #ifdef AM_DEV_KNOBS
         if constexpr (TBX == WIDE_TILE_ROWS) {
             if (g_wide_dbg & 2) return;                     // timing experiment: MFMA pipeline only
         }
 #endif
-        const unsigned jbase = (unsigned)(qtile * TBX) + L.wm * (MT * 32) + L.h * 4;
+        const unsigned jbase = (unsigned)(qtile * TBX) + L.wm * (MT * QT) + L.h * 4;
         if constexpr (ACC_INIT) {
             float xsm[NT];                                    // the diagonal tile holds both directions itself: no column-direction hit
 #pragma unroll
@@ -345,7 +346,7 @@ struct KnnFastEpilogue {
             for (int mt = 0; mt < MT; ++mt) {
                 f32x4 tqs[4];
 #pragma unroll
-                for (int g4 = 0; g4 < 4; ++g4) tqs[g4] = *reinterpret_cast<const f32x4*>(a + TBX + mt * 32 + g4 * 8);
+                for (int g4 = 0; g4 < 4; ++g4) tqs[g4] = *reinterpret_cast<const f32x4*>(a + TBX + mt * QT + g4 * GS);
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt) {
                     float amax4[4], wmax4[4];
@@ -384,7 +385,7 @@ struct KnnFastEpilogue {
                                 const int below = __builtin_amdgcn_mbcnt_hi((unsigned)(sel >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)sel, 0u));
                                 const int slot = wq + below;
                                 wq += __popcll(sel);
-                                const unsigned j = jbase + mt * 32 + g4 * 8 + e;
+                                const unsigned j = jbase + mt * QT + g4 * GS + e;
 #ifdef AM_DEV_KNOBS
                                 if (TBX == WIDE_TILE_ROWS && (g_wide_dbg & 32)) continue;
 #endif
@@ -407,8 +408,8 @@ struct KnnFastEpilogue {
             f32x4 yn[4], tq[4];
 #pragma unroll
             for (int g4 = 0; g4 < 4; ++g4) {
-                yn[g4] = *reinterpret_cast<const f32x4*>(a + mt * 32 + g4 * 8);
-                tq[g4] = *reinterpret_cast<const f32x4*>(a + TBX + mt * 32 + g4 * 8);
+                yn[g4] = *reinterpret_cast<const f32x4*>(a + mt * QT + g4 * GS);
+                tq[g4] = *reinterpret_cast<const f32x4*>(a + TBX + mt * QT + g4 * GS);
             }
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) {
@@ -456,7 +457,7 @@ struct KnnFastEpilogue {
                             const int below = __builtin_amdgcn_mbcnt_hi((unsigned)(sel >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)sel, 0u));
                             const int slot = wq + below;
                             wq += __popcll(sel);
-                            const unsigned j = jbase + mt * 32 + g4 * 8 + e;
+                            const unsigned j = jbase + mt * QT + g4 * GS + e;
                             // filed under its own row, or (mirrored only) under row j
 #ifdef AM_DEV_KNOBS
                             if (TBX == WIDE_TILE_ROWS && (g_wide_dbg & 32)) continue;     // timing experiment: entries found, not stored

@@ -1,23 +1,35 @@
 // The two 256-row f16 FILTER kernels of the PRDC path on the OPERAND-STATIONARY engine (pstat_engine.h): the bodies of
 // wide_kernels.h - membership filter, symmetric k-NN sweep - with the workgroup's P block held in registers for the whole
 // work item and only Q slabs streaming through LDS.  Rows of up to 512 f16 (D <= 512); wider sets keep wide_engine.h
-// (pairwise_wide.hip).  Same queue protocol, same accumulator values, same results; built as its own translation unit so
+// (pairwise_wide.hip).  Same queue protocol, same results (the 16x16x32 body: other accumulator values); its own translation unit so
 // that the three PRDC objects compile in parallel.
 #include "wide_kernels.h"
 #include "pstat_engine.h"
+#include <type_traits>
 
 namespace am {
 
-template <int KSLABS>
+// S16: the 16x16x32 body of the engine (pstat16_pipeline) instead of the 32x32x16 one.  Which instantiations take it is decided
+// here, per kernel: a body switches where it stays inside the register file and was measured faster at its width
+// (profiles/mfma_shape/).  The membership filter at KSLABS = 8 without row minima does (255 registers).  The k-NN sweep at
+// KSLABS = 8 does not fit: two 16-row P tiles per lane double its lane-local lists and per-row state, and the KCAP = 6 body
+// came out at 256 registers plus 60 bytes of scratch (KCAP = 11 used every register before).  Everything else keeps the 32-shape
+// until it is measured.
+template <int KSLABS, bool S16 = false>
 struct PstatEng {
-    using Lane = PLane;
+    using Lane = std::conditional_t<S16, P16Lane, PLane>;
     static constexpr int LDS_WORDS = pstat_lds_words(KSLABS);
+    static constexpr bool cross16(bool want_min) { return KSLABS == 8 && !want_min; }
+    static constexpr bool knn16(int) { return false; }
     template <class TileMap, class Epi>
     static __device__ __forceinline__ void run(const float* Q, int64_t nq, int64_t ldq, const TileMap& tm, const float* P, int64_t np,
                                                int64_t ldp, int64_t prow0, int ntiles, int, float* lds, Lane& L, Epi& epi) {
-        pstat_pipeline<KSLABS>(Q, nq, ldq, tm, P, np, ldp, prow0, ntiles, lds, L, epi);
+        if constexpr (S16) pstat16_pipeline<KSLABS>(Q, nq, ldq, tm, P, np, ldp, prow0, ntiles, lds, L, epi);
+        else pstat_pipeline<KSLABS>(Q, nq, ldq, tm, P, np, ldp, prow0, ntiles, lds, L, epi);
     }
 };
+template <int KSLABS, bool WANT_MIN> using CrossPstatEng = PstatEng<KSLABS, PstatEng<KSLABS>::cross16(WANT_MIN)>;
+template <int KSLABS, int KCAP> using KnnPstatEng = PstatEng<KSLABS, PstatEng<KSLABS>::knn16(KCAP)>;
 
 // rows of up to P64_MAX_SLABS slabs (D <= 128): 256 threads, two workgroups per CU, a wave = 64 P rows x 64-row Q units
 template <int KSLABS>
@@ -40,7 +52,7 @@ cross_pstat_kernel(const float* __restrict__ Rb, int64_t Nr, int64_t ldr, const 
                    unsigned* __restrict__ row_cover, int32_t* __restrict__ col_count, uint2* __restrict__ wgq, int qcap,
                    int* __restrict__ wgq_count, uint2* __restrict__ items, uint2* __restrict__ ovq, int* __restrict__ ov_count,
                    int ovcap, int* __restrict__ fail, float fc) {
-    cross_wide_body<PstatEng<KSLABS>, WANT_MIN>(Rb, Nr, ldr, rnorm, rthr, Cb, Nc, ldc, cnorm, cthr, Dh, nchunks, grp_rows, maxn, rmin_approx,
+    cross_wide_body<CrossPstatEng<KSLABS, WANT_MIN>, WANT_MIN>(Rb, Nr, ldr, rnorm, rthr, Cb, Nc, ldc, cnorm, cthr, Dh, nchunks, grp_rows, maxn, rmin_approx,
                                                 row_any, row_cover, col_count, wgq, qcap, wgq_count, items, ovq, ov_count, ovcap, fail, fc);
 }
 
@@ -51,7 +63,7 @@ knn_pstat_kernel(const float* __restrict__ Xb, int64_t N, int64_t ldh, const flo
                  int* __restrict__ cnt, int cap, uint2* __restrict__ wgq, float* __restrict__ wgv, int qcap,
                  int* __restrict__ wgq_count, int part, int nparts, float fc, uint2* __restrict__ ovq, float* __restrict__ ovv,
                  unsigned long long* __restrict__ ovn, int ovcap, const int* __restrict__ skip, int* __restrict__ region_counter) {
-    knn_wide_body<PstatEng<KSLABS>, KCAP>(Xb, N, ldh, xnorm, thr, Dh, win_tiles, nwin, per_win, k1, maxn, partial, cnt, cap, wgq, wgv, qcap,
+    knn_wide_body<KnnPstatEng<KSLABS, KCAP>, KCAP>(Xb, N, ldh, xnorm, thr, Dh, win_tiles, nwin, per_win, k1, maxn, partial, cnt, cap, wgq, wgv, qcap,
                                           wgq_count, part, nparts, fc, ovq, ovv, ovn, ovcap, skip, region_counter);
 }
 
@@ -122,7 +134,7 @@ static int launch_cross_pstat_t(unsigned blocks, const float* Rb, int64_t Nr, in
                                 int grp_rows, const unsigned* maxn, unsigned* rmin_approx, unsigned* row_any, unsigned* row_cover,
                                 int32_t* col_count, uint2* wgq, int qcap, int* wgq_count, uint2* items, uint2* ovq, int* ov_count,
                                 int ovcap, int* fail, float fc, hipStream_t st) {
-    constexpr size_t lds_bytes = wide_cross_lds_bytes<PstatEng<KSLABS>>();
+    constexpr size_t lds_bytes = wide_cross_lds_bytes<CrossPstatEng<KSLABS, WANT_MIN>>();
     AM_HIP_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(&cross_pstat_kernel<KSLABS, WANT_MIN>), (int)lds_bytes));
 #ifdef AM_DEV_KNOBS
     AM_HIP_TRY(set_pstat_dev_symbols(st));
@@ -190,7 +202,7 @@ static int launch_knn_pstat_t(unsigned nwg, const float* Xb, int64_t N, int64_t 
                               int win_tiles, int nwin, int per_win, int k1, const unsigned* maxn, float* partial, int* cnt, int cap,
                               uint2* wgq, float* wgv, int qcap, int* wgq_count, int part, int nparts, float fc, uint2* ovq,
                               float* ovv, unsigned long long* ovn, int ovcap, const int* skip, int* region_counter, hipStream_t st) {
-    constexpr size_t lds_bytes = knn_wide_lds_bytes<PstatEng<KSLABS>>();
+    constexpr size_t lds_bytes = knn_wide_lds_bytes<KnnPstatEng<KSLABS, KCAP>>();
     AM_HIP_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(&knn_pstat_kernel<KSLABS, KCAP>), (int)lds_bytes));
 #ifdef AM_DEV_KNOBS
     AM_HIP_TRY(set_pstat_dev_symbols(st));

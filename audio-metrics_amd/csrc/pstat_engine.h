@@ -20,7 +20,8 @@
 //
 // LDS image of a slot: 128 rows of 128 B, 16-B chunks XOR-swizzled by (row >> 1) & 7 (wide_engine.h).  MFMA roles, k order and
 // therefore every accumulator value are those of wide_engine.h: P rows lane-local (MFMA column = lane & 31), Q rows in the
-// registers, logical chunk 2c + h of slab kt in k-step 4 kt + c.
+// registers, logical chunk 2c + h of slab kt in k-step 4 kt + c.  (pstat16_pipeline below, the 16x16x32 body, accumulates in
+// another order: its accumulator values differ in the last bits, the results behind the exact re-evaluation do not.)
 //
 // Hazards (MI355X_MICROARCH.md, "LDS-DMA requests stay in flight across s_barrier"):
 //   RAW  stage g + 2 is read (first: the pre-read at the end of stage g + 1) only after the barrier that ends stage g, before
@@ -58,6 +59,8 @@ struct PLane {
     // element = 0.15 ms per sweep at 100 000 rows, at D = 128 and at D = 512 alike), and the start values are the same LDS
     // reads the epilogue did anyway.
     static constexpr bool ACC_INIT = true;
+    // accumulator geometry (32x32x16 MFMA): register 4 g4 + e of a tile <-> Q row g4 * GSTRIDE + 4 * (lane group) + e of its QT rows
+    static constexpr int GSTRIDE = 8, GROUPS = 2, QT = 32;
     int tid, lane, wave, wm, r, h;
     __device__ __forceinline__ PLane() {
         tid = threadIdx.x;
@@ -235,6 +238,208 @@ __device__ __forceinline__ void pstat_pipeline(const float* __restrict__ Q, int6
     __syncthreads();
 }
 
+// ---- the same engine on the 16x16x32 MFMA -------------------------------------------------------------------------------------
+//
+// The f16 matrix pipe is power-limited here, and the clock the chip holds depends on the MFMA shape: the same stage on
+// v_mfma_f32_16x16x32_f16 takes the same cycles at a 1.11 x higher clock (tools/ubench/pstat.hip shape,
+// profiles/mfma_shape/ubench_pstat_shape.txt: 1.50 -> 1.35 us per 8.4 MFLOP of a CU).  Same 512 threads, same ring, LDS image,
+// fill path, counted vmcnt and barriers - the hazard reasoning at the top of this file carries over word for word - but another
+// accumulation order inside the matrix core: the accumulator VALUES differ from pstat_pipeline's in the last bits (fast_c(D)
+// prices D + 1 terms in any order), the RESULTS behind the exact re-evaluation do not.
+//   * P (MFMA B): wave w owns P rows 32 w .. 32 w + 31 as TWO 16-row tiles; lane = (r = lane & 15, g = lane >> 4); the fragment
+//     of the k-step of 32 elements is the 16 B at element offset 8 g: 16 registers per slab and wave, as above;
+//   * Q (MFMA A): eight 16-row tiles per stage, two k-steps per slab: 16 ds_read_b128 per wave and stage, as above, each feeding
+//     two MFMAs; the lane reads chunk (4 c + g) ^ ((r >> 1) & 7) of row 16 mt + r.  Every lane group of a ds_read_b128 lands on
+//     sixteen distinct 16-B columns (column = 8 (r & 1) + ((4 c + g) ^ s), s = (r >> 1) & 7; a group holds every s twice with
+//     g = g0 for s in {0, 1, 6, 7} and g0 ^ 1 for s in {2 .. 5}, and s -> g(s) ^ s is a bijection of 0 .. 7);
+//   * 32 MFMAs of 16 cycles per wave and stage; a ring of four fragment registers: the fragment of tile mt + 4 is read right
+//     behind the MFMAs of tile mt (three MFMA gaps = 96 cycles ahead, as above); the two DMA pieces behind tile 1 of either k-step;
+//   * 64 accumulator registers as acc[2][2] composites of four 16 x 16 outputs: register 4 t + v of acc[m][nt] holds Q row
+//     64 m + 16 t + 4 g + v of the unit, P row 16 nt + r of the wave.
+struct P16Lane {
+    static constexpr int NT = 2;                      // 16-row P tiles per wave
+    static constexpr int MT = 2;                      // 64-row accumulator tiles of a unit
+    static constexpr int WAVES = 8;
+    static constexpr int LISTS = 4;                   // partial per-row lists after the sweep: the four lane groups
+    static constexpr bool ACC_INIT = true;
+    static constexpr int GSTRIDE = 16, GROUPS = 4, QT = 64;
+    int tid, lane, wave, wm, r, h;                    // h = lane group
+    __device__ __forceinline__ P16Lane() {
+        tid = threadIdx.x;
+        lane = tid & 63;
+        wave = tid >> 6;
+        wm = 0;
+        r = lane & 15;
+        h = lane >> 4;
+    }
+    __device__ __forceinline__ int prow(int nt) const { return wave * 32 + nt * 16 + r; }
+    __device__ __forceinline__ int list_slot() const { return h; }
+};
+
+template <int KSLABS, class TileMap, class Epi>
+__device__ __forceinline__ void pstat16_pipeline(const float* __restrict__ Q, int64_t nq, int64_t ldq, const TileMap& tmap,
+                                                 const float* __restrict__ P, int64_t np, int64_t ldp, int64_t prow0, int ntiles,
+                                                 float* __restrict__ lds, P16Lane& L, Epi& epi) {
+    static_assert(KSLABS >= 1 && KSLABS <= 8, "P fragments of at most 512 f16 per row fit the register file");
+    static_assert(Epi::ACC_INIT, "the epilogues of this engine start their accumulators at the column norm");
+    constexpr int KREG = KSLABS < PREG_SLABS ? KSLABS : PREG_SLABS;      // slabs of the P rows held in registers
+    constexpr int KLDS = KSLABS - KREG;                                   // ... and in LDS
+    constexpr int KSTEPS = KREG * 2;                  // k-steps of 32 elements
+    constexpr int PIECES = 2;
+    constexpr int DEPTH = 3;
+    const int wave = __builtin_amdgcn_readfirstlane(L.wave);
+
+    // ---- the stationary operand: two 16-row tiles
+    f32x4 pf[2][KSTEPS];
+    {
+        const TileRsrc prs = make_wide_rsrc(P, ldp, np, prow0, 0);
+#pragma unroll
+        for (int nt = 0; nt < 2; ++nt) {
+            const unsigned vop = (unsigned)(((int64_t)(wave * 32 + nt * 16 + L.r) * ldp + L.h * 4) * 4);
+#pragma unroll
+            for (int s = 0; s < KSTEPS; ++s)
+                pf[nt][s] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(prs.rsrc, (int)vop, s * 64, 0));
+        }
+        // the slabs kept in LDS: the image and the pieces of pstat_pipeline
+        const int lr8 = L.lane >> 3, s8 = L.lane & 7;
+#pragma unroll
+        for (int sl = 0; sl < KLDS; ++sl)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int row = wave * 32 + i * 8 + lr8;
+                const unsigned vo = (unsigned)(((int64_t)row * ldp + (s8 ^ ((row >> 1) & 7)) * 4) * 4);
+                lds_direct_b128(prs, lds + PRING * PSTAGE_WORDS + sl * WTB * WROW + (wave * 32 + i * 8) * WROW, vo, (unsigned)((KREG + sl) * 128));
+            }
+    }
+    const float* plds = lds + PRING * PSTAGE_WORDS + wave * 32 * WROW;     // this wave's rows of LDS slab 0
+
+    // ---- Q slabs: the pieces of pstat_pipeline
+    const int lr = L.lane >> 3, slot8 = L.lane & 7;
+    const unsigned voq0 = (unsigned)(((int64_t)lr * ldq + (slot8 ^ ((lr >> 1) & 7)) * 4) * 4);
+    const unsigned odd_soff = (unsigned)((int64_t)8 * ldq * 4);
+    const unsigned wave_soff = (unsigned)((int64_t)wave * 16 * ldq * 4), half_soff = (unsigned)((int64_t)PQ_ROWS * ldq * 4);
+    const int64_t q_tiles_total = (nq + WTB - 1) / WTB;
+    auto qtile_of = [&](int t) -> int64_t { return t < ntiles ? tmap(t) : q_tiles_total; };   // past the end: empty descriptor
+    int ft = 0, fh = 0, fk = 0, fslot = 0;
+    TileRsrc qrs = make_wide_rsrc(Q, ldq, nq, qtile_of(0) * WTB);
+    auto fetch_stage = [&](int i) {
+        float* dst = lds + fslot * PSTAGE_WORDS + (wave * 2 + i) * 8 * WROW;
+        lds_direct_b128(qrs, dst, i == 0 ? voq0 : (voq0 ^ 64u), (unsigned)(fk * 128) + (fh ? half_soff : 0u) + wave_soff + (i == 0 ? 0u : odd_soff));
+    };
+    auto advance_fetch = [&]() {
+        fslot = (fslot + 1) & (PRING - 1);
+        if (++fk == KSLABS) {
+            fk = 0;
+            fh ^= 1;
+            if (fh == 0) {
+                ++ft;
+                qrs = make_wide_rsrc(Q, ldq, nq, qtile_of(ft) * WTB);
+            }
+        }
+    };
+
+    // fragment addresses: logical 16-B chunk 4c+g of row r sits in slot (4c+g) ^ ((r >> 1) & 7); tiles lie 16 rows apart
+    const int sw = (L.r >> 1) & 7;
+    int coff[2];
+#pragma unroll
+    for (int c = 0; c < 2; ++c) coff[c] = L.r * WROW + ((4 * c + L.h) ^ sw) * 4;
+    auto qfrag = [&](int ring_slot, int c, int mt) -> f32x4 {
+        return *reinterpret_cast<const f32x4*>(lds + ring_slot * PSTAGE_WORDS + mt * 16 * WROW + coff[c]);
+    };
+    auto pfrag_lds = [&](int step, int nt) -> f32x4 {
+        return *reinterpret_cast<const f32x4*>(plds + (step / 2 - KREG) * WTB * WROW + nt * 16 * WROW + coff[step & 1]);
+    };
+
+    f32x16 acc[2][2];
+
+#pragma unroll
+    for (int g = 0; g < DEPTH; ++g) {
+        fetch_stage(0);
+        fetch_stage(1);
+        advance_fetch();
+    }
+    epi.aux_issue(0, qtile_of(0));
+    __builtin_amdgcn_s_waitcnt(0x0F70);               // vmcnt(0): side data (and the P fragments) are here
+    epi.aux_commit(0);
+    pstat_wait<0>();
+    __builtin_amdgcn_s_barrier();
+
+    f32x4 q[4];
+    f32x4 pl[2][2];                                   // P fragments of the LDS slabs, read one k-step ahead
+    int slot = 0;
+#pragma unroll
+    for (int m = 0; m < 4; ++m) q[m] = qfrag(0, 0, m);
+    L.wm = 0;
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+        const f32x16 c0 = epi.acc_init(0, m);
+        acc[m][0] = c0;
+        acc[m][1] = c0;
+    }
+    const int units = 2 * ntiles;
+    for (int u = 0; u < units; ++u) {
+        const int t = u >> 1;
+        const bool second = (u & 1) != 0;
+#pragma unroll
+        for (int ks = 0; ks < KSLABS; ++ks) {
+            const bool last_stage = ks == KSLABS - 1;
+            const int next_slot = (slot + 1) & (PRING - 1);
+            if (last_stage && second && t + 1 < ntiles) epi.aux_issue(t + 1, qtile_of(t + 1));
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                const int step = ks * 2 + c;          // k-step of the unit; steps >= KSTEPS take their P fragments from LDS
+                if (KLDS > 0 && step + 1 >= KSTEPS && step + 1 < KSLABS * 2) {
+                    pl[(step + 1) & 1][0] = pfrag_lds(step + 1, 0);
+                    pl[(step + 1) & 1][1] = pfrag_lds(step + 1, 1);
+                }
+                const f32x4 pb0 = step < KSTEPS ? pf[0][step < KSTEPS ? step : 0] : pl[step & 1][0];
+                const f32x4 pb1 = step < KSTEPS ? pf[1][step < KSTEPS ? step : 0] : pl[step & 1][1];
+#pragma unroll
+                for (int mt = 0; mt < 8; ++mt) {
+                    const int m = mt >> 2, t4 = (mt & 3) * 4;
+#pragma unroll
+                    for (int nt = 0; nt < 2; ++nt) {
+                        f32x4 a = {acc[m][nt][t4], acc[m][nt][t4 + 1], acc[m][nt][t4 + 2], acc[m][nt][t4 + 3]};
+                        a = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, q[mt & 3]), __builtin_bit_cast(f16x8, nt == 0 ? pb0 : pb1), a, 0, 0, 0);
+                        acc[m][nt][t4] = a.x; acc[m][nt][t4 + 1] = a.y; acc[m][nt][t4 + 2] = a.z; acc[m][nt][t4 + 3] = a.w;
+                    }
+                    if (mt < 4) q[mt & 3] = qfrag(slot, c, mt + 4);
+                    else if (c == 0) q[mt & 3] = qfrag(slot, 1, mt - 4);
+                    else if (!last_stage) q[mt & 3] = qfrag(next_slot, 0, mt - 4);     // published by the barrier of the stage before
+                    if (mt == 1) fetch_stage(c);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+            advance_fetch();
+            if (last_stage) {
+                L.wm = second ? 1 : 0;
+                epi.finish(t, qtile_of(t), acc);
+                if (second && t + 1 < ntiles) epi.aux_commit(t + 1);
+            }
+            // this wave's pieces of stage g + 2 have landed; the barrier publishes that stage
+            pstat_wait<PIECES>();
+            __builtin_amdgcn_s_barrier();
+            slot = next_slot;
+            if (last_stage) {
+#pragma unroll
+                for (int m = 0; m < 4; ++m) q[m] = qfrag(slot, 0, m);
+                if (u + 1 < units) {
+                    L.wm = second ? 0 : 1;
+#pragma unroll
+                    for (int m = 0; m < 2; ++m) {
+                        const f32x16 c0 = epi.acc_init((u + 1) >> 1, m);
+                        acc[m][0] = c0;
+                        acc[m][1] = c0;
+                    }
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+    }
+    __builtin_amdgcn_s_waitcnt(0x0F70);               // the (empty) fetches past the end: nothing in flight when LDS is reused
+    __syncthreads();
+}
+
 // ---- the stationary engine for NARROW rows (round 6): KSLABS <= P64_MAX_SLABS, i.e. D <= 128 (VGGish, n_pca = 64 ...) -------------
 //
 // At D = 128 a unit of the engine above is two stages long and its epilogue (vector ALU, matrix pipe idle) is 55 % of the k-NN
@@ -267,6 +472,8 @@ struct P64Lane {
     static constexpr int WAVES = 4;
     static constexpr int LISTS = 2;
     static constexpr bool ACC_INIT = true;
+    // accumulator geometry (32x32x16 MFMA): register 4 g4 + e of a tile <-> Q row g4 * GSTRIDE + 4 * (lane group) + e of its QT rows
+    static constexpr int GSTRIDE = 8, GROUPS = 2, QT = 32;
     int tid, lane, wave, wm, r, h;
     __device__ __forceinline__ P64Lane() {
         tid = threadIdx.x;

@@ -49,6 +49,8 @@ constexpr int ENGINE_THREADS = 256;
 struct LaneInfo {
     static constexpr int NT = 2;                 // 32-row P tiles per wave (pstat_engine.h: 1)
     static constexpr bool ACC_INIT = false;      // accumulators start at zero (pstat_engine.h: at the epilogue's per-column start value)
+    // accumulator geometry (32x32x16 MFMA): register 4 g4 + e of a tile <-> Q row g4 * GSTRIDE + 4 * (lane group) + e of its QT rows
+    static constexpr int GSTRIDE = 8, GROUPS = 2, QT = 32;
     int tid, lane, wm, wn, r, h;
     __device__ __forceinline__ LaneInfo() {
         tid = threadIdx.x;

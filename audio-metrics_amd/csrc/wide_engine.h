@@ -43,6 +43,8 @@ struct WLane {
     static constexpr int WAVES = 8;
     static constexpr int LISTS = 4;                   // partial per-row lists after a sweep: Q half x lane half
     static constexpr bool ACC_INIT = false;
+    // accumulator geometry (32x32x16 MFMA): register 4 g4 + e of a tile <-> Q row g4 * GSTRIDE + 4 * (lane group) + e of its QT rows
+    static constexpr int GSTRIDE = 8, GROUPS = 2, QT = 32;
     int tid, lane, wave, wm, wn, r, h;
     __device__ __forceinline__ WLane() {
         tid = threadIdx.x;

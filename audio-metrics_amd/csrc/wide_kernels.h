@@ -19,7 +19,8 @@ template <class Eng> constexpr size_t wide_cross_lds_bytes() { return (Eng::LDS_
 template <class Lane>
 struct CrossWideEpilogue {
     static constexpr int NT = Lane::NT;
-    static constexpr int MT = Lane::MT;               // 32-row Q tiles of a finish() call: L.wm counts units of MT * 32 columns
+    static constexpr int MT = Lane::MT;               // Q tiles of QT rows of a finish() call: L.wm counts units of MT * QT columns
+    static constexpr int QT = Lane::QT, GS = Lane::GSTRIDE;
     // ACC_INIT (pstat_engine.h; the scheme of KnnFastEpilogue): accumulators start at |c_j|^2 / dsc, an element holds
     // a' = <r_i, c_j>' + |c_j|^2 / dsc and the approximate squared distance is dsc a' + |r_i|^2.  Row direction (thresholds of
     // the lane's own row): fma(dsc, max_j a'_j, |r_i|^2) against them; "any" direction (column thresholds T'_j + E'_j):
@@ -58,6 +59,16 @@ struct CrossWideEpilogue {
             else *fail = 1;
         }
     }
+    // certain members of the columns of one accumulator register, from lane 0 (mask = the rows below their threshold, j = this
+    // lane's column): lane group q holds column j + 4 (q - own group) - two groups: lanes 0-31 and lanes 32-63, four: 16 lanes each
+    __device__ __forceinline__ void count_columns(unsigned long long mask, int64_t j) {
+        constexpr int W = 64 / Lane::GROUPS;
+#pragma unroll
+        for (int q = 0; q < Lane::GROUPS; ++q) {
+            const int c = __popcll(q == Lane::GROUPS - 1 ? mask >> (q * W) : (mask >> (q * W)) & (~0ull >> (64 - W)));
+            if (c) atomicAdd(col_count + j - L.h * 4 + q * 4, c);
+        }
+    }
     // loads only: the values are first used in aux_commit, after the stage's MFMAs (an arithmetic use here would park
     // waves 0-3 on a full memory round trip at the start of the last stage of every tile)
     __device__ __forceinline__ void aux_issue(int, int64_t qtile) {
@@ -81,19 +92,19 @@ struct CrossWideEpilogue {
     // NEED_ANY = false: every row of this block already has its "any" witness - the column-threshold test (one subtraction
     // and half a min3 per accumulator element, and the threshold loads) is not compiled in
     __device__ __forceinline__ f32x16 acc_init(int t, int mt) const {
-        const float* a = aux + (t & 1) * 3 * WTB + L.wm * (MT * 32) + L.h * 4 + mt * 32;
+        const float* a = aux + (t & 1) * 3 * WTB + L.wm * (MT * QT) + L.h * 4 + mt * QT;
         f32x16 c;
 #pragma unroll
         for (int g4 = 0; g4 < 4; ++g4) {
-            const f32x4 v = *reinterpret_cast<const f32x4*>(a + g4 * 8);
+            const f32x4 v = *reinterpret_cast<const f32x4*>(a + g4 * GS);
             c[g4 * 4 + 0] = v.x; c[g4 * 4 + 1] = v.y; c[g4 * 4 + 2] = v.z; c[g4 * 4 + 3] = v.w;
         }
         return c;
     }
     template <bool WANT_MIN, bool NEED_ANY>
     __device__ __forceinline__ void finish_impl(int t, int64_t qtile, f32x16 (&acc)[MT][NT]) {
-        const float* a = aux + (t & 1) * 3 * WTB + L.wm * (MT * 32) + L.h * 4;
-        const int64_t jbase = qtile * WTB + L.wm * (MT * 32) + L.h * 4;
+        const float* a = aux + (t & 1) * 3 * WTB + L.wm * (MT * QT) + L.h * 4;
+        const int64_t jbase = qtile * WTB + L.wm * (MT * QT) + L.h * 4;
 #ifdef AM_DEV_KNOBS
         if (g_wide_dbg & 2) return;                            // timing experiment: MFMA pipeline only
 #endif
@@ -103,7 +114,7 @@ struct CrossWideEpilogue {
                 f32x4 ths[4];
                 if constexpr (NEED_ANY) {
 #pragma unroll
-                    for (int g4 = 0; g4 < 4; ++g4) ths[g4] = *reinterpret_cast<const f32x4*>(a + WTB + mt * 32 + g4 * 8);
+                    for (int g4 = 0; g4 < 4; ++g4) ths[g4] = *reinterpret_cast<const f32x4*>(a + WTB + mt * QT + g4 * GS);
                 }
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt) {
@@ -134,7 +145,7 @@ struct CrossWideEpilogue {
                         if (g_wide_dbg & 16) continue;
 #endif
                     }
-                    const float* alo = a + 2 * WTB + mt * 32;
+                    const float* alo = a + 2 * WTB + mt * QT;
 #pragma unroll
                     for (int g4 = 0; g4 < 4; ++g4) {
                         const bool row_hit = lanes_le(fmaf(dsc, amax4[g4], xn[nt]), prow_thr) != 0ull;
@@ -148,24 +159,19 @@ struct CrossWideEpilogue {
                         for (int e = 0; e < 4; ++e) {
                             const int reg = g4 * 4 + e;
                             const float u = fmaf(dsc, acc[mt][nt][reg], xn[nt]);
-                            const int64_t j = jbase + mt * 32 + g4 * 8 + e;
+                            const int64_t j = jbase + mt * QT + g4 * GS + e;
                             bool sure = false, want = false;
                             if (row_hit) {
                                 const unsigned long long mask = lanes_lt(u, tlo[nt]);
                                 sure = u < tlo[nt];
-                                if (mask != 0ull && L.lane == 0) {
-                                    const int lo = __popcll(mask & 0xffffffffull);
-                                    const int hi = __popcll(mask >> 32);
-                                    if (lo) atomicAdd(col_count + j - L.h * 4, lo);
-                                    if (hi) atomicAdd(col_count + j - L.h * 4 + 4, hi);
-                                }
+                                if (mask != 0ull && L.lane == 0) count_columns(mask, j);
                                 covf[nt] = covf[nt] || sure;
                                 want = !sure && u <= thi[nt];
                                 if constexpr (WANT_MIN) want = want || u <= m[nt] + e2[nt];
                             }
                             if constexpr (NEED_ANY) {
                                 if (acc[mt][nt][reg] - ths[g4][e] >= xsn[nt]) {
-                                    if (u < alo[g4 * 8 + e]) {                      // certain witness
+                                    if (u < alo[g4 * GS + e]) {                      // certain witness
                                         anyf[nt] = true;
                                         xsn[nt] = INFINITY;
                                     } else {
@@ -185,8 +191,8 @@ struct CrossWideEpilogue {
             f32x4 yn[4], th[4];
 #pragma unroll
             for (int g4 = 0; g4 < 4; ++g4) {
-                yn[g4] = *reinterpret_cast<const f32x4*>(a + mt * 32 + g4 * 8);
-                if constexpr (NEED_ANY) th[g4] = *reinterpret_cast<const f32x4*>(a + WTB + mt * 32 + g4 * 8);
+                yn[g4] = *reinterpret_cast<const f32x4*>(a + mt * QT + g4 * GS);
+                if constexpr (NEED_ANY) th[g4] = *reinterpret_cast<const f32x4*>(a + WTB + mt * QT + g4 * GS);
             }
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) {
@@ -228,7 +234,7 @@ struct CrossWideEpilogue {
                 // Detail path, per register group and direction, behind wave-uniform gates - those groups run without ballots
                 // and counts.  (One loop with switches, not two loops: a second unrolled copy pushes the epilogue over the
                 // compiler's unroll budget and the accumulator array into scratch.)
-                const float* alo = a + 2 * WTB + mt * 32;
+                const float* alo = a + 2 * WTB + mt * QT;
 #pragma unroll
                 for (int g4 = 0; g4 < 4; ++g4) {
                     const bool row_hit = lanes_le(tmin4[g4], prow_thr) != 0ull;
@@ -242,24 +248,19 @@ struct CrossWideEpilogue {
                     for (int e = 0; e < 4; ++e) {
                         const int reg = g4 * 4 + e;
                         const float u = fmaf(dsc, acc[mt][nt][reg], xn[nt] + yn[g4][e]);
-                        const int64_t j = jbase + mt * 32 + g4 * 8 + e;
+                        const int64_t j = jbase + mt * QT + g4 * GS + e;
                         bool sure = false, want = false;
                         if (row_hit) {
                             sure = u < tlo[nt];
                             const unsigned long long mask = lanes_lt(u, tlo[nt]);
-                            if (mask != 0ull && L.lane == 0) {               // lanes 0-31: column j, lanes 32-63: column j + 4
-                                const int lo = __popcll(mask & 0xffffffffull);
-                                const int hi = __popcll(mask >> 32);
-                                if (lo) atomicAdd(col_count + j - L.h * 4, lo);
-                                if (hi) atomicAdd(col_count + j - L.h * 4 + 4, hi);
-                            }
+                            if (mask != 0ull && L.lane == 0) count_columns(mask, j);
                             covf[nt] = covf[nt] || sure;
                             want = !sure && u <= thi[nt];
                             if constexpr (WANT_MIN) want = want || u <= m[nt] + e2[nt];
                         }
                         if constexpr (NEED_ANY) {
                             if (!anyf[nt] && u <= th[g4][e]) {
-                                if (u < alo[g4 * 8 + e]) {                      // certain witness
+                                if (u < alo[g4 * GS + e]) {                      // certain witness
                                     anyf[nt] = true;
                                     athr[nt] = -INFINITY;
                                 } else {
@@ -397,9 +398,16 @@ cross_wide_body(const float* __restrict__ Rb, int64_t Nr, int64_t ldr, const flo
     }
 #pragma unroll
     for (int nt = 0; nt < Lane::NT; ++nt) {
-        const float mn = fminf(epi.m[nt], __shfl_xor(epi.m[nt], 32));
-        const int other = __shfl_xor((int)epi.anyf[nt], 32);
-        const int other_c = __shfl_xor((int)epi.covf[nt], 32);
+        // over the lane groups that share the row (unconditionally: every lane must take part)
+        float mn = fminf(epi.m[nt], __shfl_xor(epi.m[nt], 32));
+        int other = __shfl_xor((int)epi.anyf[nt], 32);
+        int other_c = __shfl_xor((int)epi.covf[nt], 32);
+#pragma unroll
+        for (int off = 16; off >= 64 / Lane::GROUPS; off >>= 1) {
+            mn = fminf(mn, __shfl_xor(mn, off));
+            other |= __shfl_xor(other | (int)epi.anyf[nt], off);
+            other_c |= __shfl_xor(other_c | (int)epi.covf[nt], off);
+        }
         const bool any = epi.anyf[nt] || other != 0;
         const bool cov = epi.covf[nt] || other_c != 0;
         if (L.h == 0 && epi.rowok[nt]) {
