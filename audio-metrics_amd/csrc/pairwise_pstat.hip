@@ -9,7 +9,7 @@
 
 namespace am {
 
-// S16: the 16x16x32 body of the engine (pstat16_pipeline) instead of the 32x32x16 one.  Which instantiations take it is decided
+// S16: the 16x16x32 body of the engine (Pstat16Body) instead of the 32x32x16 one.  Which instantiations take it is decided
 // here, per kernel: a body switches where it stays inside the register file and was measured faster at its width
 // (profiles/mfma_shape/).  The membership filter at KSLABS = 8 without row minima does (255 registers).  The k-NN sweep at
 // KSLABS = 8 does not fit: two 16-row P tiles per lane double its lane-local lists and per-row state, and the KCAP = 6 body
@@ -24,8 +24,7 @@ struct PstatEng {
     template <class TileMap, class Epi>
     static __device__ __forceinline__ void run(const float* Q, int64_t nq, int64_t ldq, const TileMap& tm, const float* P, int64_t np,
                                                int64_t ldp, int64_t prow0, int ntiles, int, float* lds, Lane& L, Epi& epi) {
-        if constexpr (S16) pstat16_pipeline<KSLABS>(Q, nq, ldq, tm, P, np, ldp, prow0, ntiles, lds, L, epi);
-        else pstat_pipeline<KSLABS>(Q, nq, ldq, tm, P, np, ldp, prow0, ntiles, lds, L, epi);
+        pstat_pipeline<std::conditional_t<S16, Pstat16Body<KSLABS>, Pstat32Body<KSLABS>>>(Q, nq, ldq, tm, P, np, ldp, prow0, ntiles, lds, L, epi);
     }
 };
 template <int KSLABS, bool WANT_MIN> using CrossPstatEng = PstatEng<KSLABS, PstatEng<KSLABS>::cross16(WANT_MIN)>;
@@ -39,7 +38,7 @@ struct Pstat64Eng {
     template <class TileMap, class Epi>
     static __device__ __forceinline__ void run(const float* Q, int64_t nq, int64_t ldq, const TileMap& tm, const float* P, int64_t np,
                                                int64_t ldp, int64_t prow0, int ntiles, int, float* lds, Lane& L, Epi& epi) {
-        pstat64_pipeline<KSLABS>(Q, nq, ldq, tm, P, np, ldp, prow0, ntiles, lds, L, epi);
+        pstat_pipeline<Pstat64Body<KSLABS>>(Q, nq, ldq, tm, P, np, ldp, prow0, ntiles, lds, L, epi);
     }
 };
 
@@ -110,38 +109,14 @@ static hipError_t set_pstat_dev_symbols(hipStream_t st) {
 bool pstat_supported(int Dh) { return Dh % WROW == 0 && Dh / WROW >= 1 && Dh / WROW <= 8; }
 bool pstat64_supported(int Dh) { return pstat_supported(Dh) && pstat64_takes(Dh / WROW); }
 
-template <int KSLABS, bool WANT_MIN>
-static int launch_cross_pstat64_t(unsigned blocks, const float* Rb, int64_t Nr, int64_t ldr, const float* rnorm, const float* rthr,
-                                  const float* Cb, int64_t Nc, int64_t ldc, const float* cnorm, const float* cthr, int Dh, int nchunks,
-                                  int grp_rows, const unsigned* maxn, unsigned* rmin_approx, unsigned* row_any, unsigned* row_cover,
-                                  int32_t* col_count, uint2* wgq, int qcap, int* wgq_count, uint2* items, uint2* ovq, int* ov_count,
-                                  int ovcap, int* fail, float fc, hipStream_t st) {
-    constexpr size_t lds_bytes = wide_cross_lds_bytes<Pstat64Eng<KSLABS>>();
-    AM_HIP_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(&cross_pstat64_kernel<KSLABS, WANT_MIN>), (int)lds_bytes));
+// the one launch of this file: `kernel` on `blocks` workgroups of `threads` with `lds_bytes` of dynamic LDS
+template <class... Params, class... Args>
+static int launch_pstat(void (*kernel)(Params...), unsigned blocks, int threads, size_t lds_bytes, hipStream_t st, Args... args) {
+    AM_HIP_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), (int)lds_bytes));
 #ifdef AM_DEV_KNOBS
     AM_HIP_TRY(set_pstat_dev_symbols(st));
 #endif
-    hipLaunchKernelGGL((cross_pstat64_kernel<KSLABS, WANT_MIN>), dim3(blocks), dim3(P64_THREADS), lds_bytes, st, Rb, Nr, ldr, rnorm, rthr, Cb,
-                       Nc, ldc, cnorm, cthr, Dh, nchunks, grp_rows, maxn, rmin_approx, row_any, row_cover, col_count, wgq, qcap,
-                       wgq_count, items, ovq, ov_count, ovcap, fail, fc);
-    AM_LAUNCH_CHECK();
-    return AM_OK;
-}
-
-template <int KSLABS, bool WANT_MIN>
-static int launch_cross_pstat_t(unsigned blocks, const float* Rb, int64_t Nr, int64_t ldr, const float* rnorm, const float* rthr,
-                                const float* Cb, int64_t Nc, int64_t ldc, const float* cnorm, const float* cthr, int Dh, int nchunks,
-                                int grp_rows, const unsigned* maxn, unsigned* rmin_approx, unsigned* row_any, unsigned* row_cover,
-                                int32_t* col_count, uint2* wgq, int qcap, int* wgq_count, uint2* items, uint2* ovq, int* ov_count,
-                                int ovcap, int* fail, float fc, hipStream_t st) {
-    constexpr size_t lds_bytes = wide_cross_lds_bytes<CrossPstatEng<KSLABS, WANT_MIN>>();
-    AM_HIP_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(&cross_pstat_kernel<KSLABS, WANT_MIN>), (int)lds_bytes));
-#ifdef AM_DEV_KNOBS
-    AM_HIP_TRY(set_pstat_dev_symbols(st));
-#endif
-    hipLaunchKernelGGL((cross_pstat_kernel<KSLABS, WANT_MIN>), dim3(blocks), dim3(PTHREADS), lds_bytes, st, Rb, Nr, ldr, rnorm, rthr, Cb, Nc,
-                       ldc, cnorm, cthr, Dh, nchunks, grp_rows, maxn, rmin_approx, row_any, row_cover, col_count, wgq, qcap, wgq_count,
-                       items, ovq, ov_count, ovcap, fail, fc);
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(threads), lds_bytes, st, args...);
     AM_LAUNCH_CHECK();
     return AM_OK;
 }
@@ -151,67 +126,27 @@ int launch_cross_pstat(bool want_min, unsigned blocks, const float* Rb, int64_t 
                        int grp_rows, const unsigned* maxn, unsigned* rmin_approx, unsigned* row_any, unsigned* row_cover,
                        int32_t* col_count, uint2* wgq, int qcap, int* wgq_count, uint2* items, uint2* ovq, int* ov_count, int ovcap,
                        int* fail, float fc, hipStream_t st) {
-#define AM_PSTAT64_CROSS(KS)                                                                                                        \
-    case KS:                                                                                                                        \
-        return want_min ? launch_cross_pstat64_t<KS, true>(blocks, Rb, Nr, ldr, rnorm, rthr, Cb, Nc, ldc, cnorm, cthr, Dh, nchunks, \
-                                                           grp_rows, maxn, rmin_approx, row_any, row_cover, col_count, wgq, qcap,   \
-                                                           wgq_count, items, ovq, ov_count, ovcap, fail, fc, st)                    \
-                        : launch_cross_pstat64_t<KS, false>(blocks, Rb, Nr, ldr, rnorm, rthr, Cb, Nc, ldc, cnorm, cthr, Dh, nchunks,\
-                                                            grp_rows, maxn, rmin_approx, row_any, row_cover, col_count, wgq, qcap,  \
-                                                            wgq_count, items, ovq, ov_count, ovcap, fail, fc, st);
+    const auto launch = [&](auto* kernel, int threads, size_t lds_bytes) {
+        return launch_pstat(kernel, blocks, threads, lds_bytes, st, Rb, Nr, ldr, rnorm, rthr, Cb, Nc, ldc, cnorm, cthr, Dh, nchunks, grp_rows,
+                            maxn, rmin_approx, row_any, row_cover, col_count, wgq, qcap, wgq_count, items, ovq, ov_count, ovcap, fail, fc);
+    };
+    // (the LDS of a kernel is a function of its engine's form and KSLABS alone)
+#define AM_PSTAT_CROSS(KERNEL, ENG, THREADS, KS)                                                                       \
+    case KS:                                                                                                          \
+        return want_min ? launch(&KERNEL<KS, true>, THREADS, wide_cross_lds_bytes<ENG<KS>>())                          \
+                        : launch(&KERNEL<KS, false>, THREADS, wide_cross_lds_bytes<ENG<KS>>());
     if (pstat64_takes(Dh / WROW)) {
-        switch (Dh / WROW) { AM_PSTAT64_CROSS(1) AM_PSTAT64_CROSS(2) }
+        switch (Dh / WROW) { AM_PSTAT_CROSS(cross_pstat64_kernel, Pstat64Eng, P64_THREADS, 1) AM_PSTAT_CROSS(cross_pstat64_kernel, Pstat64Eng, P64_THREADS, 2) }
     }
-#undef AM_PSTAT64_CROSS
-#define AM_PSTAT_CROSS(KS)                                                                                                          \
-    case KS:                                                                                                                        \
-        return want_min ? launch_cross_pstat_t<KS, true>(blocks, Rb, Nr, ldr, rnorm, rthr, Cb, Nc, ldc, cnorm, cthr, Dh, nchunks,   \
-                                                         grp_rows, maxn, rmin_approx, row_any, row_cover, col_count, wgq, qcap,     \
-                                                         wgq_count, items, ovq, ov_count, ovcap, fail, fc, st)                      \
-                        : launch_cross_pstat_t<KS, false>(blocks, Rb, Nr, ldr, rnorm, rthr, Cb, Nc, ldc, cnorm, cthr, Dh, nchunks,  \
-                                                          grp_rows, maxn, rmin_approx, row_any, row_cover, col_count, wgq, qcap,    \
-                                                          wgq_count, items, ovq, ov_count, ovcap, fail, fc, st);
+#define AM_PSTAT512_CROSS(KS) AM_PSTAT_CROSS(cross_pstat_kernel, PstatEng, PTHREADS, KS)
     switch (Dh / WROW) {
-        AM_PSTAT_CROSS(1) AM_PSTAT_CROSS(2) AM_PSTAT_CROSS(3) AM_PSTAT_CROSS(4)
-        AM_PSTAT_CROSS(5) AM_PSTAT_CROSS(6) AM_PSTAT_CROSS(7) AM_PSTAT_CROSS(8)
+        AM_PSTAT512_CROSS(1) AM_PSTAT512_CROSS(2) AM_PSTAT512_CROSS(3) AM_PSTAT512_CROSS(4)
+        AM_PSTAT512_CROSS(5) AM_PSTAT512_CROSS(6) AM_PSTAT512_CROSS(7) AM_PSTAT512_CROSS(8)
     }
+#undef AM_PSTAT512_CROSS
 #undef AM_PSTAT_CROSS
     set_error("the operand-stationary membership filter holds rows of up to 512 f16 (got %d words)", Dh);
     return AM_ERR_BAD_SHAPE;
-}
-
-template <int KSLABS, int KCAP>
-static int launch_knn_pstat64_t(unsigned nwg, const float* Xb, int64_t N, int64_t ldh, const float* xnorm, float* thr, int Dh,
-                                int win_tiles, int nwin, int per_win, int k1, const unsigned* maxn, float* partial, int* cnt, int cap,
-                                uint2* wgq, float* wgv, int qcap, int* wgq_count, int part, int nparts, float fc, uint2* ovq,
-                                float* ovv, unsigned long long* ovn, int ovcap, const int* skip, int* region_counter, hipStream_t st) {
-    constexpr size_t lds_bytes = knn_wide_lds_bytes<Pstat64Eng<KSLABS>>();
-    AM_HIP_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(&knn_pstat64_kernel<KSLABS, KCAP>), (int)lds_bytes));
-#ifdef AM_DEV_KNOBS
-    AM_HIP_TRY(set_pstat_dev_symbols(st));
-#endif
-    hipLaunchKernelGGL((knn_pstat64_kernel<KSLABS, KCAP>), dim3(nwg), dim3(P64_THREADS), lds_bytes, st, Xb, N, ldh, xnorm, thr, Dh, win_tiles,
-                       nwin, per_win, k1, maxn, partial, cnt, cap, wgq, wgv, qcap, wgq_count, part, nparts, fc, ovq, ovv, ovn, ovcap, skip,
-                       region_counter);
-    AM_LAUNCH_CHECK();
-    return AM_OK;
-}
-
-template <int KSLABS, int KCAP>
-static int launch_knn_pstat_t(unsigned nwg, const float* Xb, int64_t N, int64_t ldh, const float* xnorm, float* thr, int Dh,
-                              int win_tiles, int nwin, int per_win, int k1, const unsigned* maxn, float* partial, int* cnt, int cap,
-                              uint2* wgq, float* wgv, int qcap, int* wgq_count, int part, int nparts, float fc, uint2* ovq,
-                              float* ovv, unsigned long long* ovn, int ovcap, const int* skip, int* region_counter, hipStream_t st) {
-    constexpr size_t lds_bytes = knn_wide_lds_bytes<KnnPstatEng<KSLABS, KCAP>>();
-    AM_HIP_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(&knn_pstat_kernel<KSLABS, KCAP>), (int)lds_bytes));
-#ifdef AM_DEV_KNOBS
-    AM_HIP_TRY(set_pstat_dev_symbols(st));
-#endif
-    hipLaunchKernelGGL((knn_pstat_kernel<KSLABS, KCAP>), dim3(nwg), dim3(PTHREADS), lds_bytes, st, Xb, N, ldh, xnorm, thr, Dh, win_tiles,
-                       nwin, per_win, k1, maxn, partial, cnt, cap, wgq, wgv, qcap, wgq_count, part, nparts, fc, ovq, ovv, ovn, ovcap, skip,
-                       region_counter);
-    AM_LAUNCH_CHECK();
-    return AM_OK;
 }
 
 int launch_knn_pstat(int kcap, unsigned nwg, const float* Xb, int64_t N, int64_t ldh, const float* xnorm, float* thr, int Dh,
@@ -219,30 +154,23 @@ int launch_knn_pstat(int kcap, unsigned nwg, const float* Xb, int64_t N, int64_t
                      uint2* wgq, float* wgv, int qcap, int* wgq_count, int part, int nparts, float fc, uint2* ovq, float* ovv,
                      unsigned long long* ovn, int ovcap, const int* skip, int* region_counter, hipStream_t st) {
     AM_REQUIRE(kcap == 6 || kcap == 11, AM_ERR_UNSUPPORTED_K, "the 256-row k-NN sweep holds lists of 6 or 11 entries (got %d)", kcap);
-#define AM_PSTAT64_KNN(KS)                                                                                                          \
-    case KS:                                                                                                                        \
-        return kcap == 6 ? launch_knn_pstat64_t<KS, 6>(nwg, Xb, N, ldh, xnorm, thr, Dh, win_tiles, nwin, per_win, k1, maxn, partial,\
-                                                       cnt, cap, wgq, wgv, qcap, wgq_count, part, nparts, fc, ovq, ovv, ovn, ovcap, \
-                                                       skip, region_counter, st)                                                    \
-                         : launch_knn_pstat64_t<KS, 11>(nwg, Xb, N, ldh, xnorm, thr, Dh, win_tiles, nwin, per_win, k1, maxn,        \
-                                                        partial, cnt, cap, wgq, wgv, qcap, wgq_count, part, nparts, fc, ovq, ovv,   \
-                                                        ovn, ovcap, skip, region_counter, st);
+    const auto launch = [&](auto* kernel, int threads, size_t lds_bytes) {
+        return launch_pstat(kernel, nwg, threads, lds_bytes, st, Xb, N, ldh, xnorm, thr, Dh, win_tiles, nwin, per_win, k1, maxn, partial, cnt, cap,
+                            wgq, wgv, qcap, wgq_count, part, nparts, fc, ovq, ovv, ovn, ovcap, skip, region_counter);
+    };
+#define AM_PSTAT_KNN(KERNEL, ENG, THREADS, KS)                                                                         \
+    case KS:                                                                                                          \
+        return kcap == 6 ? launch(&KERNEL<KS, 6>, THREADS, knn_wide_lds_bytes<ENG<KS>>())                              \
+                         : launch(&KERNEL<KS, 11>, THREADS, knn_wide_lds_bytes<ENG<KS>>());
     if (pstat64_takes(Dh / WROW)) {
-        switch (Dh / WROW) { AM_PSTAT64_KNN(1) AM_PSTAT64_KNN(2) }
+        switch (Dh / WROW) { AM_PSTAT_KNN(knn_pstat64_kernel, Pstat64Eng, P64_THREADS, 1) AM_PSTAT_KNN(knn_pstat64_kernel, Pstat64Eng, P64_THREADS, 2) }
     }
-#undef AM_PSTAT64_KNN
-#define AM_PSTAT_KNN(KS)                                                                                                            \
-    case KS:                                                                                                                        \
-        return kcap == 6 ? launch_knn_pstat_t<KS, 6>(nwg, Xb, N, ldh, xnorm, thr, Dh, win_tiles, nwin, per_win, k1, maxn, partial,  \
-                                                     cnt, cap, wgq, wgv, qcap, wgq_count, part, nparts, fc, ovq, ovv, ovn, ovcap,   \
-                                                     skip, region_counter, st)                                                      \
-                         : launch_knn_pstat_t<KS, 11>(nwg, Xb, N, ldh, xnorm, thr, Dh, win_tiles, nwin, per_win, k1, maxn, partial, \
-                                                      cnt, cap, wgq, wgv, qcap, wgq_count, part, nparts, fc, ovq, ovv, ovn, ovcap,  \
-                                                      skip, region_counter, st);
+#define AM_PSTAT512_KNN(KS) AM_PSTAT_KNN(knn_pstat_kernel, PstatEng, PTHREADS, KS)
     switch (Dh / WROW) {
-        AM_PSTAT_KNN(1) AM_PSTAT_KNN(2) AM_PSTAT_KNN(3) AM_PSTAT_KNN(4)
-        AM_PSTAT_KNN(5) AM_PSTAT_KNN(6) AM_PSTAT_KNN(7) AM_PSTAT_KNN(8)
+        AM_PSTAT512_KNN(1) AM_PSTAT512_KNN(2) AM_PSTAT512_KNN(3) AM_PSTAT512_KNN(4)
+        AM_PSTAT512_KNN(5) AM_PSTAT512_KNN(6) AM_PSTAT512_KNN(7) AM_PSTAT512_KNN(8)
     }
+#undef AM_PSTAT512_KNN
 #undef AM_PSTAT_KNN
     set_error("the operand-stationary k-NN sweep holds rows of up to 512 f16 (got %d words)", Dh);
     return AM_ERR_BAD_SHAPE;

@@ -826,7 +826,7 @@ int am_prdc_path(int64_t Nr, int64_t Nc, int D);
 int am_kd_path(int64_t N1, int64_t ldx, int64_t N2, int64_t ldy, int D, int m, int degree, int rbf);
 /* form 3 has three tile engines, chosen by the row length alone: 1 = operand-stationary (csrc/pstat_engine.h: the workgroup's
  * 256-row block held in registers, kernels knn_pstat_kernel / cross_pstat_kernel; rows of up to 512 elements),
- * 2 = the same as two independent 256-thread workgroups per CU whose waves own two row tiles (pstat64_pipeline: kernels
+ * 2 = the same as two independent 256-thread workgroups per CU whose waves own two row tiles (Pstat64Body: kernels
  * knn_pstat64_kernel / cross_pstat64_kernel; rows of up to 128 elements),
  * 0 = both operands streamed through LDS (csrc/wide_engine.h: knn_wide_kernel / cross_wide_kernel) */
 int am_filter_engine(int D);

@@ -1,5 +1,7 @@
 """The stationary f16 filter engine at the widths whose kernels may run on the 16x16x32 MFMA (csrc/pstat_engine.h,
-pstat16_pipeline; which instantiation takes it: PstatEng in csrc/pairwise_pstat.hip).
+Pstat16Body; which instantiation takes it: PstatEng in csrc/pairwise_pstat.hip), and at the one width with exactly ONE slab
+of the P rows in LDS (KSLABS = 7, D = 385 ... 448): there the engine's two-entry ring of LDS P fragments alternates between a
+register slab and the LDS slab at the boundary.
 
 Another MFMA shape means another register-to-(row, column) mapping in the epilogues and another accumulation order: the
 approximate values and the queued pairs change, the results behind the exact re-evaluation may not.  Shapes are the smallest
@@ -19,6 +21,7 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 pytestmark = pytest.mark.gpu
 
 WIDTHS = [512, 500]            # KSLABS = 8: two slabs of the P rows in LDS; 500 is padded to 512
+WIDTHS7 = [448, 440]           # KSLABS = 7: one slab in LDS; 440 is padded to 448
 N_RADII = 6411
 NR, NC = 4111, 4203
 
@@ -47,7 +50,7 @@ def sets(probe):
 
 
 @pytest.mark.parametrize("k", [5, 10])
-@pytest.mark.parametrize("d", WIDTHS)
+@pytest.mark.parametrize("d", WIDTHS + WIDTHS7)
 @pytest.mark.parametrize("fam", ["randn", "unit"])
 def test_radii(probe, fam, d, k):
     ops = probe.ops
@@ -63,7 +66,7 @@ def test_radii(probe, fam, d, k):
 
 
 @pytest.mark.parametrize("want_min", [False, True])
-@pytest.mark.parametrize("d", WIDTHS)
+@pytest.mark.parametrize("d", WIDTHS + WIDTHS7[:1])
 @pytest.mark.parametrize("fam", ["randn", "unit"])
 def test_membership_counts(probe, sets, fam, d, want_min):
     ops = probe.ops

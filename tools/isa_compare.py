@@ -1,0 +1,64 @@
+#!/usr/bin/env python3
+"""Compare the instruction streams of the kernels in two device assembly files (hipcc --cuda-device-only -S).
+
+    python tools/isa_compare.py parent.s change.s [name-substring]
+
+Each file is split at its kernel labels; comments, directives and blank lines are dropped, and what remains of each kernel
+(instructions and local labels) is compared text for text.  For a kernel that differs the differing lines and the counts of
+the instructions that make up a pipeline stage are printed.  Exit status 0: the same kernels, every one identical."""
+import difflib
+import re
+import sys
+
+COUNTED = [("mfma", r"^v_mfma"), ("ds_read_b128", r"^ds_read_b128"), ("lds-dma", r"^buffer_load_dword.*\blds\b"),
+           ("s_barrier", r"^s_barrier"), ("s_waitcnt", r"^s_waitcnt")]
+
+
+def kernels(path, want):
+    out, name, body = {}, None, None
+    kernel_names = set()
+    with open(path) as f:
+        lines = f.read().splitlines()
+    for line in lines:
+        m = re.match(r"\s*\.amdhsa_kernel\s+(\S+)", line)
+        if m:
+            kernel_names.add(m.group(1))
+    for line in lines:
+        m = re.match(r"(\w+):", line)
+        if m and m.group(1) in kernel_names:
+            name, body = m.group(1), []
+            continue
+        if name is None:
+            continue
+        if re.match(r"\.Lfunc_end\d+:", line):
+            if want in name:
+                out[name] = body
+            name = None
+            continue
+        text = line.split(";")[0].strip()
+        if text and not (text.startswith(".") and not text.endswith(":")):
+            body.append(re.sub(r"\s+", " ", text))
+    return out
+
+
+def counts(body):
+    return {key: sum(1 for line in body if re.match(rx, line)) for key, rx in COUNTED}
+
+
+def main():
+    a, b = kernels(sys.argv[1], sys.argv[3] if len(sys.argv) > 3 else ""), kernels(sys.argv[2], sys.argv[3] if len(sys.argv) > 3 else "")
+    bad = 0
+    for name in sorted(set(a) | set(b)):
+        if name not in a or name not in b:
+            print(f"ONLY IN {'first' if name in a else 'second'}: {name}")
+            bad += 1
+        elif a[name] != b[name]:
+            bad += 1
+            print(f"DIFFERS: {name}\n  first:  {len(a[name])} lines {counts(a[name])}\n  second: {len(b[name])} lines {counts(b[name])}")
+            sys.stdout.write("\n".join(difflib.unified_diff(a[name], b[name], "first", "second", n=0, lineterm="")) + "\n")
+    print(f"{len(a)} / {len(b)} kernels, {len(set(a) & set(b)) - sum(1 for n in set(a) & set(b) if a[n] != b[n])} identical, {bad} not")
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
