@@ -40,6 +40,18 @@ SIGNATURES = {
     "am_frechet_groups_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
     "am_frechet_groups_f32": (c_int, [_P, c_int64, c_int64, c_int, _P, _P, c_int, _P, _P, _P, _P, c_size_t, _P]),
     "am_frechet_groups_f64": (c_int, [_P, c_int64, c_int64, c_int, _P, _P, c_int, _P, _P, _P, _P, c_size_t, _P]),
+    "am_vendi_groups_max_rows": (c_int, []),
+    "am_vendi_groups_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
+    "am_vendi_groups_f32": (c_int, [_P, c_int64, c_int64, c_int, _P, _P, c_int, c_int, c_double, _P, _P, _P, _P, c_size_t, _P]),
+    "am_vendi_groups_f64": (c_int, [_P, c_int64, c_int64, c_int, _P, _P, c_int, c_int, c_double, _P, _P, _P, _P, c_size_t, _P]),
+    "am_vendi_gram_max_rows": (c_int, []),
+    "am_vendi_gram_workspace_bytes": (c_size_t, [c_int64, c_int]),
+    "am_vendi_gram_f32": (c_int, [_P, c_int64, c_int64, c_int, _P, c_int64, c_int, c_double, _P, _P, _P, c_size_t, _P]),
+    "am_vendi_gram_f64": (c_int, [_P, c_int64, c_int64, c_int, _P, c_int64, c_int, c_double, _P, _P, _P, c_size_t, _P]),
+    "am_vendi_moment_chunks": (c_int, [c_int64, c_int]),
+    "am_vendi_moment_workspace_bytes": (c_size_t, [c_int64, c_int]),
+    "am_vendi_moment_f32": (c_int, [_P, c_int64, c_int64, c_int, _P, _P, c_size_t, _P]),
+    "am_vendi_moment_f64": (c_int, [_P, c_int64, c_int64, c_int, _P, _P, c_size_t, _P]),
     "am_apa_f64": (c_double, [c_double, c_double, c_double]),
     "am_kd_workspace_bytes": (c_size_t, [c_int, c_int]),
     "am_kd_poly_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),

@@ -18,28 +18,14 @@
 // Every reduction runs in a fixed order: the call is deterministic.
 #include "am_common.h"
 #include "groups_common.h"
+#include "jacobi_lds.h"
 
 namespace am {
 
 constexpr int FG_MAX_ROWS = 128;      // 128 x 129 f64 = 129 KiB of the CU's 160 KiB LDS
-constexpr int FG_MAX_SWEEPS = 30;
-constexpr double FG_EPS = 2.220446049250313e-16;     // 2^-52
 constexpr int FG_TILE = 64, FG_KT = 16, FG_LDT = 80;  // pass 2: tile edge, k step, LDS row stride (f64)
 
 typedef double fg_f64x4 __attribute__((ext_vector_type(4)));
-
-// sum of one value per thread of a 256-thread workgroup, as a fixed tree; every thread receives it
-__device__ __forceinline__ double fg_block_sum(double v, double* red) {
-    const int t = threadIdx.x;
-    __syncthreads();
-    red[t] = v;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (t < s) red[t] += red[t + s];
-        __syncthreads();
-    }
-    return red[0];
-}
 
 // ---------------------------------------------------------------- pass 1: means, centred rows, the three scalar terms
 template <class T>
@@ -155,27 +141,12 @@ __global__ void __launch_bounds__(256) fg_gemm_kernel(const double* __restrict__
 }
 
 // ---------------------------------------------------------------- pass 3: M into LDS, Jacobi, the record
-// t-th pair (a <= b) of the h x h triangle, t < ceil(h / 2) * (h + 1): row a' of an (h + 1)-wide rectangle holds row a' of the
-// triangle followed by row h - 1 - a'.  Returns false for the second half of the middle row of an odd h (a duplicate).
-__device__ __forceinline__ bool fg_fold_decode(int t, int h, int& a, int& b) {
-    const int ap = t / (h + 1), bp = t - ap * (h + 1);
-    if (bp < h - ap) {
-        a = ap;
-        b = ap + bp;
-        return true;
-    }
-    a = h - 1 - ap;
-    b = a + (bp - (h - ap));
-    return a != ap;
-}
-
 template <int MCAP>
 __global__ void __launch_bounds__(256) fg_solve_kernel(const double* __restrict__ xc, const double* __restrict__ z,
                                                        const int64_t* __restrict__ offs, int D, const double* __restrict__ stats,
                                                        double* __restrict__ out) {
-    constexpr int LDM = MCAP + 1;                                      // odd stride: a column walk touches every bank
-    constexpr int HCAP = MCAP / 2;
-    constexpr int NBLK = (HCAP * (HCAP + 1) / 2 + 255) / 256;          // 2 x 2 blocks of the a <= b half per thread
+    constexpr int LDM = JacobiLds<MCAP>::LDM;
+    constexpr int HCAP = JacobiLds<MCAP>::HCAP;
     __shared__ double M[MCAP * LDM];
     __shared__ double red[256];
     __shared__ double rc[HCAP], rs[HCAP], rt[HCAP];                    // the round's rotations: cos, sin, tan
@@ -197,7 +168,6 @@ __global__ void __launch_bounds__(256) fg_solve_kernel(const double* __restrict_
         return;
     }
     const int m = n + (n & 1);                                         // an odd group gets one all-zero dummy index
-    const int h = m / 2;
     for (int e = tid; e < m * LDM; e += 256) M[e] = 0.0;
     __syncthreads();
 
@@ -236,91 +206,10 @@ __global__ void __launch_bounds__(256) fg_solve_kernel(const double* __restrict_
     }
     __syncthreads();
 
-    // ---- this thread's 2 x 2 blocks (pairs of rotation slots a <= b); the same in every round
-    int blk_a[NBLK], blk_b[NBLK];
-    const int nfold = ((h + 1) / 2) * (h + 1);
-#pragma unroll
-    for (int u = 0; u < NBLK; ++u) {
-        const int t = tid + u * 256;
-        int a = 0, bb = 0;
-        const bool ok = t < nfold && fg_fold_decode(t, h, a, bb);
-        blk_a[u] = ok ? a : -1;
-        blk_b[u] = bb;
-    }
-
-    double fro2 = 0.0;
-    for (int e = tid; e < m * m; e += 256) {
-        const double v = M[(e / m) * LDM + e % m];
-        fro2 += v * v;
-    }
-    fro2 = fg_block_sum(fro2, red);
-    const double fro = sqrt(fro2);
-    int sweeps = 0, stop = 0;
-    double off = 0.0;
-    if (!(fro2 - fro2 == 0.0) || !(base - base == 0.0)) stop = 4;      // a non-finite input reached M or the scalar terms
-    while (stop == 0) {
-        double off2 = 0.0;
-        for (int e = tid; e < m * m; e += 256) {
-            const int i = e / m, j = e - i * m;
-            const double v = M[i * LDM + j];
-            off2 += i != j ? v * v : 0.0;
-        }
-        off2 = fg_block_sum(off2, red);
-        off = sqrt(off2);
-        if (!(off2 - off2 == 0.0)) { stop = 4; break; }
-        if (off <= FG_EPS * fro) { stop = 1; break; }
-        if (sweeps == FG_MAX_SWEEPS) { stop = 2; break; }
-        for (int r = 0; r < m - 1; ++r) {
-            if (tid < h) {                                               // round-robin pairing: index m - 1 stays, the rest turn
-                int p, q;
-                if (tid == 0) {
-                    p = r;
-                    q = m - 1;
-                } else {
-                    p = r + tid;
-                    if (p >= m - 1) p -= m - 1;
-                    q = r - tid;
-                    if (q < 0) q += m - 1;
-                }
-                const double app = M[p * LDM + p], aqq = M[q * LDM + q], apq = M[p * LDM + q];
-                double c = 1.0, s = 0.0, tn = 0.0;
-                if (apq != 0.0) {
-                    const double theta = (aqq - app) / (2.0 * apq);
-                    tn = copysign(1.0, theta) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                    c = 1.0 / sqrt(tn * tn + 1.0);
-                    s = tn * c;
-                }
-                rp[tid] = p; rq[tid] = q; rc[tid] = c; rs[tid] = s; rt[tid] = tn;
-            }
-            __syncthreads();
-#pragma unroll
-            for (int u = 0; u < NBLK; ++u) {
-                const int a = blk_a[u], bb = blk_b[u];
-                if (a < 0) continue;
-                const int pa = rp[a], qa = rq[a], pb = rp[bb], qb = rq[bb];
-                if (a == bb) {                                           // the pivot block: the off-diagonal element becomes 0
-                    const double apq = M[pa * LDM + qa], tn = rt[a];
-                    M[pa * LDM + pa] -= tn * apq;
-                    M[qa * LDM + qa] += tn * apq;
-                    M[pa * LDM + qa] = 0.0;
-                    M[qa * LDM + pa] = 0.0;
-                } else {
-                    const double ca = rc[a], sa = rs[a], cb = rc[bb], sb = rs[bb];
-                    const double x00 = M[pa * LDM + pb], x01 = M[pa * LDM + qb], x10 = M[qa * LDM + pb], x11 = M[qa * LDM + qb];
-                    const double y00 = ca * x00 - sa * x10, y01 = ca * x01 - sa * x11;
-                    const double y10 = sa * x00 + ca * x10, y11 = sa * x01 + ca * x11;
-                    const double z00 = cb * y00 - sb * y01, z01 = sb * y00 + cb * y01;
-                    const double z10 = cb * y10 - sb * y11, z11 = sb * y10 + cb * y11;
-                    M[pa * LDM + pb] = z00; M[pb * LDM + pa] = z00;
-                    M[pa * LDM + qb] = z01; M[qb * LDM + pa] = z01;
-                    M[qa * LDM + pb] = z10; M[pb * LDM + qa] = z10;
-                    M[qa * LDM + qb] = z11; M[qb * LDM + qa] = z11;
-                }
-            }
-            __syncthreads();
-        }
-        ++sweeps;
-    }
+    // ---- the cyclic Jacobi of jacobi_lds.h; a non-finite scalar term stops the group as a non-finite M does
+    double fro, off;
+    int sweeps;
+    const int stop = fg_jacobi_lds<MCAP>(M, JacobiLds<MCAP>{red, rc, rs, rt, rp, rq}, m, !(base - base == 0.0), fro, off, sweeps);
 
     // ---- eigenvalues at or below 4 n 2^-52 lambda_max count as zero; the rest add their square roots in index order
     if (tid == 0) {

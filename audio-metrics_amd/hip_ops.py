@@ -555,6 +555,129 @@ def frechet_groups(rows, idx, offsets, mu_y, cov_y, out=None):
     return out, _index_check(ws, idx, n, "group rows")
 
 
+# ------------------------------------------------------------------ Vendi score
+VENDI_KERNELS = {"cosine": 0, "gaussian": 1}                 # enum am_vendi_kernel
+_VENDI_CAPS = {}
+
+
+def vendi_groups_max_rows():
+    if "groups" not in _VENDI_CAPS:
+        _VENDI_CAPS["groups"] = int(_lib.load().am_vendi_groups_max_rows())
+    return _VENDI_CAPS["groups"]
+
+
+def vendi_gram_max_rows():
+    if "gram" not in _VENDI_CAPS:
+        _VENDI_CAPS["gram"] = int(_lib.load().am_vendi_gram_max_rows())
+    return _VENDI_CAPS["gram"]
+
+
+def _vendi_kernel_args(kernel, gamma, gamma_dev):
+    """(kernel code, gamma, gamma_dev pointer) of the am_vendi_* entry points; no device call.  The cosine kernel takes no
+    width; the Gaussian one exactly one of a number and a float32 device scalar holding a median squared distance."""
+    if kernel not in VENDI_KERNELS:
+        raise ValueError(f"kernel={kernel!r} must be one of {sorted(VENDI_KERNELS)}")
+    if kernel == "cosine":
+        if gamma is not None or gamma_dev is not None:
+            raise ValueError("the cosine kernel takes neither gamma nor gamma_dev")
+        return 0, 0.0, ctypes.c_void_p(None)
+    dev_arg, gamma_arg = _bandwidth_args(gamma_dev, gamma)
+    if gamma_dev is None and not (gamma_arg > 0.0 and gamma_arg < float("inf")):
+        raise ValueError(f"gamma={gamma!r} must be a finite positive number")
+    return 1, gamma_arg, dev_arg
+
+
+def _whole_set_check(ws, idx, n, noun):
+    """check() of am_vendi_gram_* / am_vendi_moment_*: the one host read of the two flag words at the head of the
+    workspace.  An index outside [0, n) raises ValueError; a row without a similarity (zero norm, or a non-finite element)
+    is returned as its position, None when every row has one."""
+    def check():
+        flags = ws[:16].view(torch.int64).cpu().tolist()
+        if flags[0] != 0:
+            pos = flags[0] - 1
+            bad = int(idx[pos].item()) if idx is not None else pos
+            raise ValueError(f"idx[{pos}] = {bad} is outside [0, {n}) ({noun} are named by stored-row index)")
+        return flags[1] - 1 if flags[1] != 0 else None
+    return check
+
+
+def vendi_groups(rows, idx, offsets, kernel="cosine", gamma=None, gamma_dev=None):
+    """The eigenvalues of K / n and the order-1 Vendi score of every group of rows (am_vendi_groups_f32 / _f64, by the dtype
+    of rows; the group list as frechet_groups takes it), every group of 1 .. vendi_groups_max_rows() rows.  kernel:
+    "cosine", or "gaussian" with exactly one of gamma (a number) and gamma_dev (a float32 device scalar holding a median
+    squared distance: gamma = 0.5 / it, formed on the device).  Nothing waits for the device: returns (rec, evals, check)
+    with rec the f64 device tensor [B, 8] of { vendi, entropy, rank, lambda_max, sweeps, residual, stop code, 0 } records,
+    evals the f64 device tensor [n_total] of each group's eigenvalues at its list positions (descending, those at or below
+    4 n 2^-52 lambda_max as 0), and check() the one host read of the workspace's flag word, which raises ValueError for an
+    index outside [0, N)."""
+    code, gamma_arg, dev_arg = _vendi_kernel_args(kernel, gamma, gamma_dev)
+    offs, b, host_offs = _group_offsets(offsets)
+    lib = _lib.load()
+    f64 = is_f64(rows)
+    rows = as_rows(rows)
+    n, d = rows.shape
+    dev = rows.device
+    if gamma_dev is not None:
+        _same_device(rows, gamma_dev)
+    idx = _group_index(idx, offs[-1], rows)
+    rec = torch.empty((b, 8), dtype=torch.float64, device=dev)
+    evals = torch.empty(offs[-1], dtype=torch.float64, device=dev)
+    nb = lib.am_vendi_groups_workspace_bytes(offs[-1], b, d)
+    ws = _workspace(nb, dev)
+    _call(lib, "am_vendi_groups_f64" if f64 else "am_vendi_groups_f32", dev, _ptr(rows), n, _ld64(rows) if f64 else _ld(rows), d,
+          _ptr(idx) if idx is not None else ctypes.c_void_p(None), ctypes.cast(host_offs, ctypes.c_void_p), b, code, gamma_arg, dev_arg,
+          _ptr(rec), _ptr(evals), _ptr(ws), nb)
+    return rec, evals, _index_check(ws, idx, n, "group rows")
+
+
+def vendi_gram(rows, idx=None, kernel="cosine", gamma=None, gamma_dev=None):
+    """M = K / n of the rows rows[idx] (idx None: all rows) as an f64 device tensor [n, n] (am_vendi_gram_f32 / _f64):
+    exactly symmetric, diagonal exactly 1 / n, n <= vendi_gram_max_rows().  Returns (m, check); nothing waits for the
+    device.  check() raises ValueError for an index outside [0, N) and returns the position of a row without a similarity
+    (zero norm under the cosine kernel, or a non-finite element; such a row counts as zeros in m), or None."""
+    code, gamma_arg, dev_arg = _vendi_kernel_args(kernel, gamma, gamma_dev)
+    n_rows = int(rows.shape[0]) if idx is None else int(idx.numel())
+    if not 1 <= n_rows <= vendi_gram_max_rows():
+        raise ValueError(f"vendi_gram takes 1 .. {vendi_gram_max_rows()} rows, got {n_rows}")
+    lib = _lib.load()
+    f64 = is_f64(rows)
+    rows = as_rows(rows)
+    n, d = rows.shape
+    dev = rows.device
+    if gamma_dev is not None:
+        _same_device(rows, gamma_dev)
+    idx = _group_index(idx, n_rows, rows)
+    m = torch.empty((n_rows, n_rows), dtype=torch.float64, device=dev)
+    nb = lib.am_vendi_gram_workspace_bytes(n_rows, d)
+    ws = _workspace(nb, dev)
+    _call(lib, "am_vendi_gram_f64" if f64 else "am_vendi_gram_f32", dev, _ptr(rows), n, _ld64(rows) if f64 else _ld(rows), d,
+          _ptr(idx) if idx is not None else ctypes.c_void_p(None), n_rows, code, gamma_arg, dev_arg, _ptr(m), _ptr(ws), nb)
+    return m, _whole_set_check(ws, idx, n, "rows")
+
+
+def vendi_moment_chunks(n, d):
+    """The number of row chunks am_vendi_moment_* folds for n rows of d columns (a host query)."""
+    return int(_lib.load().am_vendi_moment_chunks(int(n), int(d)))
+
+
+def vendi_moment(rows):
+    """S = (1 / n) sum_i x_i x_i^T / |x_i|^2 over all rows as an f64 device tensor [D, D] (am_vendi_moment_f32 / _f64): the
+    dual form of the cosine kernel's K / n, with the same non-zero eigenvalues.  Returns (s, check) as vendi_gram does."""
+    if rows.dim() != 2 or rows.shape[0] < 1:
+        raise ValueError(f"vendi_moment takes a non-empty 2-D matrix of rows, got shape {tuple(rows.shape)}")
+    lib = _lib.load()
+    f64 = is_f64(rows)
+    rows = as_rows(rows)
+    n, d = rows.shape
+    dev = rows.device
+    s = torch.empty((d, d), dtype=torch.float64, device=dev)
+    nb = lib.am_vendi_moment_workspace_bytes(n, d)
+    ws = _workspace(nb, dev)
+    _call(lib, "am_vendi_moment_f64" if f64 else "am_vendi_moment_f32", dev, _ptr(rows), n, _ld64(rows) if f64 else _ld(rows), d, _ptr(s),
+          _ptr(ws), nb)
+    return s, _whole_set_check(ws, None, n, "rows")
+
+
 class FrechetJob:
     """A Frechet solve in flight on a side stream (frechet_async).  Nothing here blocks the host until .result()."""
 

@@ -210,6 +210,68 @@ int am_frechet_groups_f64(const double* X, int64_t N, int64_t ld, int D,
                           const double* mu_y, const double* cov_y,
                           double* out_dev, void* ws, size_t ws_bytes, am_stream_t stream);
 
+/* The Vendi score (Friedman & Dieng 2023; orders q: Pasarkar & Dieng 2023): a reference-free diversity number, "the
+ * effective number of distinct samples".  For n rows x_i with G = X X^T accumulated in f64 (float32 rows are converted on
+ * load, which is exact: the _f32 and _f64 entry points return the SAME BITS on the same values):
+ *   AM_VENDI_COSINE    K_ij = G_ij / (sqrt(G_ii) sqrt(G_jj))
+ *   AM_VENDI_GAUSSIAN  K_ij = exp(-gamma max(G_ii + G_jj - 2 G_ij, 0)), gamma = 1 / (2 bw^2), the rows as they are
+ * with K_ii = 1 exactly; M = K / n is symmetric PSD with trace 1 and eigenvalues lambda_i.  Eigenvalues <= zero_tol *
+ * lambda_max count as zero, rank = the number that remain, and over those, in descending order,
+ *   order 1: exp(-sum lambda ln lambda)     order inf: 1 / lambda_max     other q > 0: (sum lambda^q)^(1 / (1 - q)).
+ * zero_tol DEPENDS ON THE ROUTE: the per-group Jacobi resolves null eigenvalues at rounding level and uses
+ * 4 n_b 2^-52; the eigenvalues of the whole-set matrices come from am_eigh_sym_f64, whose pinned accuracy is 1e-10 lambda_0,
+ * so callers of am_vendi_gram_* / am_vendi_moment_* use zero_tol = 1e-10.  The rule matters for q < 1: a null eigenvalue
+ * left at 1e-17 contributes (1e-17)^0.1 = 0.02, and duplicate rows make exact null vectors.
+ * gamma_dev != NULL (a float32 DEVICE scalar holding a median squared distance, as the KAD kernels take it): gamma =
+ * 0.5 / (double)*gamma_dev, no host synchronisation; else the host double `gamma` (finite, > 0) is used.  Cosine ignores both.
+ *
+ * am_vendi_groups_*: B groups of rows of ONE stored matrix, the group-list protocol of am_frechet_groups_* (idx DEVICE or
+ * NULL = stored order, offsets HOST; an index outside [0, N) is never dereferenced, counts as a zero row and is reported
+ * through the first 8 bytes of `ws`), 1 <= n_b <= am_vendi_groups_max_rows() (128).  One workgroup per group: the rows are
+ * gathered straight from X (no copy), the upper triangle of G comes from v_mfma_f64_16x16x4_f64 and is mirrored in LDS, the
+ * kernel transform is applied there, and the cyclic Jacobi of am_frechet_groups_* (round-robin, stop at off-norm <= 2^-52
+ * |M|_F, at most 30 sweeps) gives the eigenvalues.
+ *   out_rec    DEVICE [B][8]: { vendi (order 1), entropy, rank, lambda_max, sweeps, residual, stop code, 0 }; stop codes as
+ *              am_frechet_groups_*: 1 = converged, 2 = sweep cap, 4 = non-finite input
+ *   out_evals  DEVICE [n_total]: each group's eigenvalues at its list positions, descending, thresholded ones as 0.0
+ * n_b == 1: vendi = 1, entropy 0, rank 1, no sweeps, stop code 1.  A row of zero norm (cosine) or with a non-finite element:
+ * NaN record and eigenvalues for ITS group, stop code 4; no other group is affected.  No floating-point atomics, fixed
+ * reduction orders: a group's record does not depend on B, its neighbours, idx versus stored order, or the row type.
+ *
+ * am_vendi_gram_*: out_m DEVICE [n][n] = K / n for the rows idx[0..n) (idx == NULL: rows 0 .. n - 1), n <=
+ * am_vendi_gram_max_rows() (2048, else AM_ERR_BAD_SHAPE): upper 64 x 64 tiles computed and mirrored (exactly symmetric),
+ * diagonal exactly 1 / n, every element written once.
+ * am_vendi_moment_*: out_s DEVICE [D][D] = (1 / n) sum_i x_i x_i^T / |x_i|^2 over all N rows - the cosine kernel's dual form:
+ * K / n and S share their non-zero eigenvalues.  The rows are cut into am_vendi_moment_chunks(N, D) chunks whose partial
+ * matrices are folded in chunk order; the upper triangle is computed and mirrored.
+ * Both: `ws` opens with TWO flag words - [0] 1 + the position of an index outside [0, N), [1] 1 + the position of a row of
+ * zero norm (cosine / moment) or with a non-finite element - or 0; such rows count as zeros. */
+enum am_vendi_kernel { AM_VENDI_COSINE = 0, AM_VENDI_GAUSSIAN = 1 };
+int am_vendi_groups_max_rows(void);
+size_t am_vendi_groups_workspace_bytes(int64_t n_total, int B, int D);
+int am_vendi_groups_f32(const float* X, int64_t N, int64_t ld, int D,
+                        const int64_t* idx, const int64_t* offsets, int B,
+                        int kernel, double gamma, const float* gamma_dev,
+                        double* out_rec, double* out_evals, void* ws, size_t ws_bytes, am_stream_t stream);
+int am_vendi_groups_f64(const double* X, int64_t N, int64_t ld, int D,
+                        const int64_t* idx, const int64_t* offsets, int B,
+                        int kernel, double gamma, const float* gamma_dev,
+                        double* out_rec, double* out_evals, void* ws, size_t ws_bytes, am_stream_t stream);
+int am_vendi_gram_max_rows(void);
+size_t am_vendi_gram_workspace_bytes(int64_t n, int D);
+int am_vendi_gram_f32(const float* X, int64_t N, int64_t ld, int D, const int64_t* idx, int64_t n,
+                      int kernel, double gamma, const float* gamma_dev,
+                      double* out_m, void* ws, size_t ws_bytes, am_stream_t stream);
+int am_vendi_gram_f64(const double* X, int64_t N, int64_t ld, int D, const int64_t* idx, int64_t n,
+                      int kernel, double gamma, const float* gamma_dev,
+                      double* out_m, void* ws, size_t ws_bytes, am_stream_t stream);
+int am_vendi_moment_chunks(int64_t n, int D);
+size_t am_vendi_moment_workspace_bytes(int64_t n, int D);
+int am_vendi_moment_f32(const float* X, int64_t N, int64_t ld, int D,
+                        double* out_s, void* ws, size_t ws_bytes, am_stream_t stream);
+int am_vendi_moment_f64(const double* X, int64_t N, int64_t ld, int D,
+                        double* out_s, void* ws, size_t ws_bytes, am_stream_t stream);
+
 /* A11 APA scalar combination (host arithmetic)  reference: apa.py:22-32 */
 double am_apa_f64(double d_y_x, double d_y_xp, double d_x_xp);
 
