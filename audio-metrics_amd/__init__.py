@@ -22,6 +22,7 @@ from .metrics.prdc import prdc, nearest_neighbour_distances                   # 
 from .metrics.neighbors import nearest_neighbors                              # noqa: F401
 from .metrics.fidelity import sample_fidelity, sample_fidelity_per_group, fidelity_by_group   # noqa: F401
 from .metrics.mauve import kmeans, mauve_score, mauve_from_histograms         # noqa: F401
+from .metrics.sinkhorn import sinkhorn_divergence, sinkhorn_schedule       # noqa: F401
 from .metrics.apa import apa, apa_compute_d_x_xp                              # noqa: F401
 from .metrics.vendi import vendi_score, vendi_score_per_group, vendi_from_eigenvalues   # noqa: F401
 

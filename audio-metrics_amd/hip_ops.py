@@ -5,6 +5,7 @@ computation below is a call into libaudio_metrics_hip.so on torch's current
 HIP stream.  There is no CPU path: CPU tensors are rejected.
 """
 import ctypes
+import math
 import os
 
 import torch
@@ -1290,6 +1291,61 @@ def kmeans_update(x, labels, c_old):
     _call(lib, "am_kmeans_update_f32", dev, _ptr(x), n, _ld(x), d, _ptr(labels), _ptr(order), _ptr(offsets), k, _ptr(c_old),
           _ld(c_old), _ptr(c_new), ld, _ptr(counts), _ptr(ws), nb)
     return c_new, counts
+
+
+# ---- soft-min: one log-domain Sinkhorn half-step (csrc/softmin.hip) ----
+def _potential_ok(t, rows):
+    return t is None or (torch.is_tensor(t) and t.dim() == 1 and t.shape[0] == rows and t.dtype == torch.float64)
+
+
+def softmin(x, y, g=None, eps=None, prev=None, damping=0.0):
+    """T_i = -eps log((1 / M) sum_j exp((g_j - |x_i - y_j|^2 / 2) / eps)) for every row of x against the M rows of y
+    (am_softmin_f32): (out float64 [N], change float64 0-d, magnitude float64 0-d) as device tensors, stream-ordered, nothing
+    waits for the device.  g: float64 [M] potentials on the rows of y (None: zeros); out = damping * prev + (1 - damping) * T
+    (damping == 0: T itself); change = max |out - prev| (prev None: max |out|), magnitude = max |out|.  The squared
+    distances have the bits of knn_search(x, y, ., squared=True); `x is y` computes the norms once.  Two calls return the
+    same bits."""
+    if is_f64(x) or is_f64(y):
+        raise NotImplementedError("softmin takes float32 rows (the float64 matrix-core form is not implemented)")
+    if x.dim() != 2 or y.dim() != 2:
+        raise ValueError(f"x and y must be 2-D, got shapes {tuple(x.shape)} and {tuple(y.shape)}")
+    if x.shape[1] != y.shape[1]:
+        raise ValueError(f"feature widths differ: {x.shape[1]} and {y.shape[1]}")
+    if x.shape[0] < 1 or y.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError(f"softmin needs rows on both sides (got shapes {tuple(x.shape)} and {tuple(y.shape)})")
+    if eps is None or not math.isfinite(float(eps)) or float(eps) <= 0.0:
+        raise ValueError(f"eps={eps!r} must be a finite positive number")
+    eps, damping = float(eps), float(damping)
+    if not 0.0 <= damping < 1.0:
+        raise ValueError(f"damping={damping!r} must lie in [0, 1)")
+    if not _potential_ok(g, y.shape[0]):
+        raise ValueError(f"g must be a float64 tensor with one potential per row of y ({y.shape[0]})")
+    if not _potential_ok(prev, x.shape[0]):
+        raise ValueError(f"prev must be a float64 tensor with one value per row of x ({x.shape[0]})")
+    if damping != 0.0 and prev is None:
+        raise ValueError(f"damping={damping!r} needs prev")
+    lib = _lib.load()
+    same = x is y
+    x = as_matrix(x, "x")
+    y = x if same else as_matrix(y, "y")
+    vectors = []
+    for t, name in ((g, "g"), (prev, "prev")):
+        if t is not None:
+            _require_cuda(t, name)
+            t = t.contiguous()
+            vectors.append(t)
+    dev = _same_device(x, y, *vectors)
+    g = g.contiguous() if g is not None else None
+    prev = prev.contiguous() if prev is not None else None
+    n, d = x.shape
+    m = y.shape[0]
+    out = torch.empty(n, dtype=torch.float64, device=dev)
+    stats = torch.empty(2, dtype=torch.float64, device=dev)
+    nb = lib.am_softmin_workspace_bytes(n, m, d)
+    ws = _workspace(nb, dev)
+    _call(lib, "am_softmin_f32", dev, _ptr(x), n, _ld(x), _ptr(y), m, _ld(y), d, _ptr(g) if g is not None else None, eps,
+          _ptr(prev) if prev is not None else None, damping, _ptr(out), _ptr(stats), _ptr(ws), nb)
+    return out, stats[0], stats[1]
 
 
 # ---- partitioned symmetric k-NN (multi-GPU, every rank holds the full set) ----

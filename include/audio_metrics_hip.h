@@ -601,6 +601,31 @@ int am_kmeans_update_f32(const float* X, int64_t N, int64_t ldx, int D,
                          void* ws, size_t ws_bytes, am_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * SOFT-MIN, one log-domain Sinkhorn half-step (csrc/softmin.hip)              no counterpart in the reference
+ *   For every row x_i of X against the M rows of Y, column potentials g (DEVICE double[M]; NULL = zeros) and a temperature
+ *   eps (HOST double):
+ *     T_i = -eps log( (1 / M) sum_j exp( (g_j - d2(x_i, y_j) / 2) / eps ) )
+ *   One Gram pass on the exact f32 tile engine, no N x M matrix: the sweep and the d2 bits of am_kmeans_assign_f32 /
+ *   am_knn_search_f32(squared) (f32 norms, same inner order, max(., 0), NaN -> +inf).  Per pair z = fmaf(-d2, (float)(0.5 /
+ *   eps), (float)(g_j / eps)) in f32; per row an online log-sum-exp: a running f32 maximum of z and the f64 sum of
+ *   exp(z - max), exp in f64.  eps log M is added once, in f64, at the end.  A column at distance +inf contributes exactly 0.
+ *     out[i]   = damping * prev[i] + (1 - damping) * T_i       DEVICE double[N]; damping (HOST double) in [0, 1); damping == 0
+ *                writes T_i itself.  prev: DEVICE double[N], may be NULL when damping == 0; out may be prev.
+ *     stats    OPTIONAL (may be NULL) DEVICE double[2], overwritten: { max_i |out[i] - prev[i]| (prev NULL: |out[i]|),
+ *                max_i |out[i]| } - the two numbers a Sinkhorn step's stop rule needs, so that a step reads nothing back
+ *   Partial (max, sum) pairs of the lanes and of the column chunks are joined in a fixed order, the two maxima are integer
+ *   maxima over bit patterns: no floating-point atomics, two calls return the same bits.  X may be Y (same pointer, rows and
+ *   stride: the norms are computed once).  eps must be finite and > 0 with 0.5 / eps a normal float32 number.  X, Y as for
+ *   am_knn_search_f32 (16-byte aligned, ld % 4 == 0, ld >= D).  Workspace: the row norms, one float per column and
+ *   [column chunks][N] (float, double) partials.  Everything is validated before the first HIP call; the call is
+ *   asynchronous.
+ * ------------------------------------------------------------------------- */
+size_t am_softmin_workspace_bytes(int64_t N, int64_t M, int D);
+int am_softmin_f32(const float* X, int64_t N, int64_t ldx, const float* Y, int64_t M, int64_t ldy, int D,
+                   const double* g, double eps, const double* prev, double damping, double* out, double* stats,
+                   void* ws, size_t ws_bytes, am_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * PER-SAMPLE realism, ball count and rarity on the PRDC manifold (csrc/sample_scores.hip)   no counterpart in the reference
  *   X: the samples (N rows), Y: the manifold set (M rows), r_y: device float[M], the k-NN radius of row j of Y (what
  *   am_knn_radii_f32(Y, Y) returns).  One Gram pass on the exact f32 tile engine, no N x M matrix.  Per pair, all in f32:
