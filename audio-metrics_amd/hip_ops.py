@@ -1230,6 +1230,50 @@ def sample_scores_chunks(n, m, d):
     return int(_lib.load().am_sample_scores_chunks(int(n), int(m), int(d)))
 
 
+# ---- probabilistic scoring rule of a point against a set (csrc/psr.hip) ----
+PSR_RADIUS_SQ_MAX = 3.4028234663852886e+38                     # FLT_MAX: the in-range threshold is a float32
+
+
+def psr_scores(x, y, radius, sums=True):
+    """PSR and in-range count of every row of x against the rows of y and ONE radius of the set y (am_psr_f32):
+    (psr float64 [N], count int32 [N], sums float64 [2] or None) as device tensors, stream-ordered, nothing waits for the
+    device.  count = #{ j : |x - y_j| < radius }, psr = 1 - prod over those j of |x - y_j| / radius (0.0 with nothing in
+    range, 1.0 on a row of y); sums = { sum psr, sum count } in a fixed tree (sums=False: not computed).  The squared
+    distances have the bits of knn_search(x, y, ., squared=True); `x is y` computes the norms once.  Two calls at the same
+    shapes return the same bits; the last bits of psr depend on the chunk plan (psr_chunks)."""
+    if is_f64(x) or is_f64(y):
+        raise NotImplementedError("psr_scores takes float32 rows (the float64 matrix-core form is not implemented)")
+    if x.dim() != 2 or y.dim() != 2:
+        raise ValueError(f"x and y must be 2-D, got shapes {tuple(x.shape)} and {tuple(y.shape)}")
+    if x.shape[1] != y.shape[1]:
+        raise ValueError(f"feature widths differ: {x.shape[1]} and {y.shape[1]}")
+    if x.shape[0] < 1 or y.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError(f"psr_scores needs rows on both sides (got shapes {tuple(x.shape)} and {tuple(y.shape)})")
+    radius = float(radius)
+    if not (math.isfinite(radius) and radius > 0.0 and radius * radius <= PSR_RADIUS_SQ_MAX):
+        raise ValueError(f"radius={radius} must be finite and > 0, with radius^2 a finite float32 number")
+    lib = _lib.load()
+    same = x is y
+    x = as_matrix(x, "x")
+    y = x if same else as_matrix(y, "y")
+    dev = _same_device(x, y)
+    n, d = x.shape
+    m = y.shape[0]
+    psr = torch.empty(n, dtype=torch.float64, device=dev)
+    count = torch.empty(n, dtype=torch.int32, device=dev)
+    totals = torch.empty(2, dtype=torch.float64, device=dev) if sums else None
+    nb = lib.am_psr_workspace_bytes(n, m, d)
+    ws = _workspace(nb, dev)
+    _call(lib, "am_psr_f32", dev, _ptr(x), n, _ld(x), _ptr(y), m, _ld(y), d, radius, _ptr(psr), _ptr(count),
+          _ptr(totals) if sums else None, _ptr(ws), nb)
+    return psr, count, totals
+
+
+def psr_chunks(n, m, d):
+    """Column chunks the plan cuts the rows of y into (am_psr_chunks; tests and tools)."""
+    return int(_lib.load().am_psr_chunks(int(n), int(m), int(d)))
+
+
 # ---- k-means: the two halves of a Lloyd iteration (csrc/kmeans.hip) ----
 def _kmeans_check(what, x, c):
     if is_f64(x) or is_f64(c):

@@ -655,6 +655,38 @@ int am_sample_scores_f32(const float* X, int64_t N, int64_t ldx, const float* Y,
                          void* ws, size_t ws_bytes, am_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * PROBABILISTIC scoring rule of a point against a set (csrc/psr.hip)                  no counterpart in the reference
+ *   The per-row quantity of probabilistic precision and recall (Park & Kim, ICCV 2023).  X: the points (N rows), Y: the
+ *   set (M rows), radius: ONE radius for the whole set Y, a HOST double.  One Gram pass on the exact f32 tile engine, no
+ *   N x M matrix.  Per pair:
+ *     d2       = max(fmaf(-2, <x_i, y_j>, |x_i|^2 + |y_j|^2), 0), NaN -> +inf: the bits of am_knn_search_f32(squared)
+ *                (same row norms, same inner order)
+ *     in range   d2 < T, T the smallest float32 >= radius * radius (the product in f64)  <=>  (double)d2 < radius * radius;
+ *                NaN and +inf are never in range
+ *     factor     fminf(fmul_rn(sqrt_rn(d2), (float)(1.0 / radius)), 1.0f) for a pair in range, in f32
+ *   Outputs per row i of X, all overwritten:
+ *     out_count[i] = #{ j : in range }
+ *     out_psr[i]   = 1.0 - prod_{j in range} factor, in f64: exactly 0.0 with no column in range, exactly 1.0 when some
+ *                    in-range d2 is 0.  Products of at most 16 factors (one lane's share of a 32 x 32 accumulator sub-tile)
+ *                    are formed in f32 - one that underflows to 0 moves psr by less than 1e-37 - everything beyond is an
+ *                    f64 running product joined in a fixed order (lane slot order, then chunk order)
+ *     out_sums     DEVICE double[2], may be NULL: { sum_i out_psr[i], sum_i out_count[i] }, f64 sums in a fixed tree; the
+ *                  second is an exact integer
+ *   No floating-point atomics: two calls at the same shapes return the same bits.  Unlike the key-based entry points
+ *   (search, assign, sample scores) the LAST BITS of out_psr DEPEND ON THE CHUNK PLAN (am_psr_chunks, a function of N and
+ *   M): an f64 product is grouped by chunk.  out_count does not.  X may be Y (nothing is skipped: every finite row then
+ *   has psr 1.0).  radius must be finite and > 0 with radius^2 <= FLT_MAX (else AM_ERR_BAD_ARG); the shape rules are those
+ *   of am_sample_scores_f32 (M < 2^32 - 1; 16-byte aligned, ld % 4 == 0, ld >= D).  Workspace: the row norms,
+ *   [am_psr_chunks][N] (double, int32) partials and the block sums.  Everything is validated before the first HIP call;
+ *   the call is asynchronous.
+ * ------------------------------------------------------------------------- */
+size_t am_psr_workspace_bytes(int64_t N, int64_t M, int D);
+int am_psr_chunks(int64_t N, int64_t M, int D);                /* column chunks of the plan (tests, tools) */
+int am_psr_f32(const float* X, int64_t N, int64_t ldx, const float* Y, int64_t M, int64_t ldy, int D,
+               double radius, double* out_psr, int32_t* out_count, double* out_sums,
+               void* ws, size_t ws_bytes, am_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * A9, partitioned form for one-process-per-GPU callers that all hold the FULL set X.
  * The self-distance matrix is bitwise symmetric, so only half of the tile pairs are multiplied
  * (csrc/pairwise.hip, knn_sym_kernel); rank `part` of `nparts` owns a contiguous range of the 128-row blocks.
