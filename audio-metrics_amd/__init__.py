@@ -10,6 +10,8 @@ from .data import AudioMetricsData, ensure_tensor, ensure_ndarray            # n
 from . import metrics                                                         # noqa: F401
 from .metrics.fad import frechet_distance, frechet_distance_inf               # noqa: F401
 from .metrics.fad import frechet_distance_per_group                           # noqa: F401
+from .metrics.fad_stats import frechet_distance_with_error, frechet_distance_compare   # noqa: F401
+from .metrics.fad_stats import frechet_standard_error, frechet_difference_test       # noqa: F401
 from .metrics.kd import kernel_distance, kid_features_to_metric               # noqa: F401
 from .metrics.kad import kernel_audio_distance                                # noqa: F401
 from .metrics.kad import kernel_audio_distance_per_group                      # noqa: F401

@@ -34,6 +34,11 @@ SIGNATURES = {
     "am_frechet_f64": (c_int, [_P, _P, _P, _P, c_int, c_int, c_double, _P, _P, c_size_t, _P]),
     "am_frechet_first_block": (c_int, []),
     "am_frechet_enqueue_f64": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_double, _P, _P, c_size_t, _P]),
+    "am_frechet_maps_workspace_bytes": (c_size_t, [c_int]),
+    "am_frechet_maps_f64": (c_int, [_P, _P, _P, _P, c_int, c_int, c_double, _P, _P, _P, _P, c_size_t, _P]),
+    "am_frechet_influence_workspace_bytes": (c_size_t, [c_int64]),
+    "am_frechet_influence_f32": (c_int, [_P, c_int64, c_int64, c_int, _P, _P, _P, c_double, _P, _P, _P, c_size_t, _P]),
+    "am_frechet_influence_f64": (c_int, [_P, c_int64, c_int64, c_int, _P, _P, _P, c_double, _P, _P, _P, c_size_t, _P]),
     "am_frechet_batch_workspace_bytes": (c_size_t, [c_int, c_int]),
     "am_frechet_batch_f64": (c_int, [_P, _P, _P, _P, c_int64, c_int, c_int, c_int, c_double, _P, _P, c_size_t, _P]),
     "am_frechet_groups_max_rows": (c_int, []),

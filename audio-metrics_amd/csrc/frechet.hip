@@ -162,6 +162,41 @@ __global__ void __launch_bounds__(256) fd_finish_kernel(const double* __restrict
     }
 }
 
+// The Gaussian optimal-transport maps from the solve's final Z -> (A / |A|_F)^(-1/2), A = Cx Cy (am_frechet_maps_f64):
+//     map_xy = sym(P) / sqrt(norm),  P = Cy Z        (the SPD matrix with map_xy Cx map_xy = Cy)
+//     map_yx = sym(Q) / sqrt(norm),  Q = Z Cx        (its inverse; (Cx Z^T)^T for symmetric Cx, and sym(B^T) = sym(B))
+// P and Q come from one launch of ns_pair_kernel (the solver's tile product); here element (i, j) adds P_ij + P_ji - the same two numbers as element (j, i), so
+// the result is exactly symmetric.  ok == 0 (the solve did not converge): both maps are filled with NaN.
+__global__ void __launch_bounds__(256) ns_pair_kernel(GemmJob j0, GemmJob j1, int n) {
+    __shared__ __attribute__((aligned(16))) double part[4 * GT * PST];
+    const GemmJob job = blockIdx.z == 0 ? j0 : j1;
+    const int row0 = blockIdx.y * GT, col0 = blockIdx.x * GT;
+    double v[4];
+    tile_product(job, n, row0, col0, part, v);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int e = threadIdx.x + 256 * q;
+        const int gr = row0 + (e >> 5), gc = col0 + (e & 31);
+        if (gr < n && gc < n) job.C[(int64_t)gr * n + gc] = v[q];
+    }
+}
+
+__global__ void __launch_bounds__(256) fd_maps_kernel(const double* __restrict__ P, const double* __restrict__ Q, int n,
+                                                      const NsState* __restrict__ state, int ok, double* __restrict__ map_xy,
+                                                      double* __restrict__ map_yx) {
+    const double scale = ok ? 0.5 / sqrt(state->norm) : 0.0;
+    const int64_t total = (int64_t)n * n;
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
+        if (!ok) {
+            map_xy[e] = map_yx[e] = __builtin_nan("");
+            continue;
+        }
+        const int64_t t = (e % n) * n + e / n;
+        map_xy[e] = (P[e] + P[t]) * scale;
+        map_yx[e] = (Q[e] + Q[t]) * scale;
+    }
+}
+
 struct NsBuffers {
     double *A, *Y[2], *Z[2], *T, *resid_sums, *trace_sums;
     NsState* state;               // [2]: ping-pong, iteration `it` reads state[it & 1] and writes state[(it + 1) & 1]
@@ -276,6 +311,52 @@ extern "C" int am_frechet_f64(const double* mu_x, const double* cov_x, const dou
         if ((int)out5[4] != 0) break;
     }
     for (int i = 0; i < 4; ++i) out_host[i] = out5[i];
+    AM_REQUIRE((int)out5[4] != 4, AM_ERR_NO_CONVERGENCE, "non-finite covariance product or trace in Newton-Schulz");
+    return AM_OK;
+}
+
+extern "C" size_t am_frechet_maps_workspace_bytes(int D) { return am_frechet_workspace_bytes(D); }
+
+// am_frechet_f64's chain, kernel for kernel, then the two maps from the final Z (see fd_maps_kernel)
+extern "C" int am_frechet_maps_f64(const double* mu_x, const double* cov_x, const double* mu_y, const double* cov_y, int D,
+                                   int max_iter, double tol, double* out_host, double* map_xy, double* map_yx, void* ws,
+                                   size_t ws_bytes, am_stream_t stream) {
+    AM_REQUIRE(mu_x && cov_x && mu_y && cov_y && out_host && map_xy && map_yx, AM_ERR_BAD_ARG, "null pointer");
+    AM_REQUIRE(D >= 1, AM_ERR_BAD_SHAPE, "D=%d", D);
+    if (max_iter <= 0) max_iter = 64;
+    if (!(tol > 0)) tol = 1e-13;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    Carver c(ws, ws_bytes);
+    NsBuffers b;
+    carve_ns(c, D, b);
+    double* out_dev = c.take<double>(8);
+    AM_REQUIRE(c.ok(), AM_ERR_WORKSPACE, "workspace too small: need %zu bytes, have %zu", c.off, ws_bytes);
+    double out5[5] = {0, 0, 0, 0, 0};
+    int fin = 0;                                      // where the block just run left the state (as enqueue_ns counts it)
+    for (int first = 0; first < max_iter;) {
+        const int n_iter = std::min(am_frechet_first_block(), max_iter - first);
+        const bool last_block = first + n_iter >= max_iter;
+        const int rc = enqueue_ns(mu_x, cov_x, mu_y, cov_y, D, first, n_iter, last_block, tol, b, out_dev, st);
+        if (rc != AM_OK) return rc;
+        AM_HIP_TRY(hipMemcpyAsync(out5, out_dev, sizeof(out5), hipMemcpyDeviceToHost, st));
+        AM_HIP_TRY(hipStreamSynchronize(st));
+        fin = ((first + n_iter) & 1) ^ (last_block ? 1 : 0);
+        first += n_iter;
+        if ((int)out5[4] != 0) break;
+    }
+    for (int i = 0; i < 5; ++i) out_host[i] = out5[i];
+    const int ok = (int)out5[4] == 1;
+    const unsigned fill_grid = (unsigned)std::min<int64_t>(256, ceil_div((int64_t)D * D, 1024));
+    if (ok) {
+        // converged at the check of iteration iters - 1, which read Y and Z from buffer (iters - 1) & 1 and wrote nothing.
+        // A and T are free once the chain has ended.
+        const double* z = b.Z[((int)out5[2] - 1) & 1];
+        hipLaunchKernelGGL(ns_pair_kernel, dim3(b.g, b.g, 2), dim3(256), 0, st, GemmJob{cov_y, z, b.A}, GemmJob{z, cov_x, b.T}, D);
+        AM_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(fd_maps_kernel, dim3(fill_grid), dim3(256), 0, st, (const double*)b.A, (const double*)b.T, D,
+                       (const NsState*)(b.state + fin), ok, map_xy, map_yx);
+    AM_LAUNCH_CHECK();
     AM_REQUIRE((int)out5[4] != 4, AM_ERR_NO_CONVERGENCE, "non-finite covariance product or trace in Newton-Schulz");
     return AM_OK;
 }

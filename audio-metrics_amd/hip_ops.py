@@ -477,7 +477,50 @@ def frechet(mu_x, cov_x, mu_y, cov_y, max_iter=64, tol=1e-13):
     return dict(fd=out[0], tr_sqrt=out[1], iters=int(out[2]), resid=out[3])
 
 
-FRECHET_BATCH_WS_CAP = 1 << 30      # bytes of solver workspace per library call; larger batches go in chunks of sets
+def frechet_maps(mu_x, cov_x, mu_y, cov_y, max_iter=64, tol=1e-13):
+    """frechet() plus the Gaussian optimal-transport maps (am_frechet_maps_f64): the dict of frechet() - the same bits -
+    with "stop" (the solver's stop code; 1 = converged), "map_xy" (the symmetric A with A cov_x A = cov_y) and "map_yx" (its
+    inverse), both f64 device [D, D], exactly symmetric, and all NaN unless stop == 1."""
+    lib = _lib.load()
+    mu_x, cov_x, mu_y, cov_y = (_f64(t, "stats") for t in (mu_x, cov_x, mu_y, cov_y))
+    d = mu_x.numel()
+    if cov_x.shape != (d, d) or cov_y.shape != (d, d) or mu_y.numel() != d:
+        raise ValueError(f"inconsistent shapes: mu {tuple(mu_x.shape)}/{tuple(mu_y.shape)}, "
+                         f"cov {tuple(cov_x.shape)}/{tuple(cov_y.shape)}")
+    dev = _same_device(mu_x, cov_x, mu_y, cov_y)
+    out = (ctypes.c_double * 5)()
+    map_xy = torch.empty((d, d), dtype=torch.float64, device=dev)
+    map_yx = torch.empty((d, d), dtype=torch.float64, device=dev)
+    nb = lib.am_frechet_maps_workspace_bytes(d)
+    ws = _workspace(nb, dev)
+    _call(lib, "am_frechet_maps_f64", dev, _ptr(mu_x), _ptr(cov_x), _ptr(mu_y), _ptr(cov_y), d, int(max_iter), float(tol),
+          ctypes.cast(out, ctypes.c_void_p), _ptr(map_xy), _ptr(map_yx), _ptr(ws), nb)
+    return dict(fd=out[0], tr_sqrt=out[1], iters=int(out[2]), resid=out[3], stop=int(out[4]), map_xy=map_xy, map_yx=map_yx)
+
+
+def frechet_influence(rows, mu, b, lin, c0):
+    """psi_i = c_i^T b c_i + lin^T c_i + c0 with c_i = rows_i - mu (am_frechet_influence_f32 / _f64, by the dtype of rows;
+    all arithmetic in f64, the same bits for float32 rows and their float64 copies).  mu, lin: f64 device [D]; b: f64 device
+    [D, D], symmetric; c0: a number.  Returns (psi f64 [N], sums f64 [4] = {sum psi, sum psi^2, finite rows, non-finite
+    rows}), both on the device; a row with a non-finite element has psi = NaN and is left out of the sums."""
+    lib = _lib.load()
+    rows = as_rows(rows, "rows")
+    f64 = is_f64(rows)
+    n, d = rows.shape
+    mu, b, lin = (_f64(t, "influence terms") for t in (mu, b, lin))
+    if n < 1 or mu.numel() != d or lin.numel() != d or tuple(b.shape) != (d, d):
+        raise ValueError(f"inconsistent shapes: rows {tuple(rows.shape)}, mu {tuple(mu.shape)}, b {tuple(b.shape)}, lin {tuple(lin.shape)}")
+    dev = _same_device(rows, mu, b, lin)
+    psi = torch.empty(n, dtype=torch.float64, device=dev)
+    sums = torch.empty(4, dtype=torch.float64, device=dev)
+    nb = lib.am_frechet_influence_workspace_bytes(n)
+    ws = _workspace(nb, dev)
+    _call(lib, "am_frechet_influence_f64" if f64 else "am_frechet_influence_f32", dev, _ptr(rows), n, _ld64(rows) if f64 else _ld(rows),
+          d, _ptr(mu), _ptr(b), _ptr(lin), float(c0), _ptr(psi), _ptr(sums), _ptr(ws), nb)
+    return psi, sums
+
+
+FRECHET_BATCH_WS_CAP = 1 << 30     # bytes of solver workspace per library call; larger batches go in chunks of sets
 
 
 def frechet_batch(mu_x, cov_x, mu_y, cov_y, max_iter=64, tol=1e-13, out=None):

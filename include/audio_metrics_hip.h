@@ -161,6 +161,47 @@ int am_frechet_enqueue_f64(const double* mu_x, const double* cov_x,
                            const double* mu_y, const double* cov_y, int D,
                            int first_iter, int n_iter, int max_iter, double tol, double* out_dev,
                            void* ws, size_t ws_bytes, am_stream_t stream);
+/* The Frechet distance together with the Gaussian optimal-transport maps between the two sets.  The chain is that of
+ * am_frechet_f64 - the same kernels in the same order - so out_host[0..3] (HOST, 5 doubles) equal am_frechet_f64's BIT FOR
+ * BIT; out_host[4] is the stop code of am_frechet_enqueue_f64.  The solve's final Z is (cov_x cov_y / norm)^(-1/2), norm =
+ * |cov_x cov_y|_F, and from it, in f64 on the matrix cores (the solver's own tile product),
+ *   map_xy = sym(cov_y Z) / sqrt(norm)      the symmetric positive definite A with A cov_x A = cov_y
+ *   map_yx = sym(Z cov_x) / sqrt(norm)      its inverse (= sym(cov_x Z^T) for a symmetric cov_x)
+ * both DEVICE [D][D]; sym(B)_ij = (B_ij + B_ji) / 2 adds the same two numbers for (i, j) and (j, i): EXACTLY symmetric.
+ * Hence d tr sqrt(cov_x cov_y) / d cov_x = map_xy / 2 and d / d cov_y = map_yx / 2: the first-order influence of a row
+ * (am_frechet_influence_*).  The maps are defined for stop code 1 (converged) only - for any other stop code BOTH ARE
+ * FILLED WITH NaN and the distance is still returned (stop code 4: the status is AM_ERR_NO_CONVERGENCE, as am_frechet_f64
+ * gives it).  Their accuracy is that of the solve: |map_xy cov_x map_xy - cov_y|_F / |cov_y|_F is about cond(cov_x cov_y)
+ * 2^-52.  Workspace: am_frechet_maps_workspace_bytes(D) (= am_frechet_workspace_bytes).  SYNCHRONISES `stream` once per
+ * block of iterations, as am_frechet_f64 does; the maps are enqueued behind that and not waited for. */
+size_t am_frechet_maps_workspace_bytes(int D);
+int am_frechet_maps_f64(const double* mu_x, const double* cov_x,
+                        const double* mu_y, const double* cov_y, int D,
+                        int max_iter, double tol, double* out_host,
+                        double* map_xy, double* map_yx,
+                        void* ws, size_t ws_bytes, am_stream_t stream);
+/* Per-row influence values  psi_i = c_i^T B c_i + lin^T c_i + c0,  c_i = x_i - mu,  for the N rows of X (row stride ld).
+ *   mu [D], B [D][D] (symmetric), lin [D]   DEVICE f64;  c0 a number
+ *   psi [N], sums [4]                        DEVICE f64;  sums = { sum psi, sum psi^2, finite psi, non-finite psi }
+ * With B = I - map_xy, lin = 2 (mu_x - mu_y), c0 = -tr(B cov_x) over the candidate rows, and B = I - map_yx, lin =
+ * -2 (mu_x - mu_y), c0 = -tr(B cov_y) over the reference rows, psi is the first-order influence of a row on the Frechet
+ * distance: var(fd) ~ s^2(psi_x) / n + s^2(psi_y) / m.
+ * Arithmetic, all in f64 for both entry points: float32 rows are converted on load (exact), so am_frechet_influence_f32
+ * returns the SAME BITS as am_frechet_influence_f64 on the same values.  One workgroup owns 64 rows, forms T = C B on
+ * v_mfma_f64_16x16x4_f64 column tile by column tile (k ascending) and folds (T_ij + lin_j) c_ij into the row's sum, columns
+ * in a fixed order; T never reaches memory.  |psi_i - exact| <= (2 D + 8) 2^-53 (|c|^T |B| |c| + |lin|^T |c| + |c0|).  A row's
+ * psi depends on that row alone (not on N, ld or its place in the tile).  A row with a NaN or inf element (or whose psi
+ * overflows) gets psi = NaN, counts as non-finite and is left out of the two sums.  The sums are added in a fixed tree -
+ * no floating-point atomics: two calls return the same bits.
+ * Limits: N >= 1, 1 <= D <= 8192, ld >= D; float32 rows 16-byte aligned with ld % 4 == 0; else AM_ERR_BAD_SHAPE.
+ * Workspace: 32 bytes per 64 rows.  Asynchronous. */
+size_t am_frechet_influence_workspace_bytes(int64_t N);
+int am_frechet_influence_f32(const float* X, int64_t N, int64_t ld, int D,
+                             const double* mu, const double* B, const double* lin, double c0,
+                             double* psi, double* sums, void* ws, size_t ws_bytes, am_stream_t stream);
+int am_frechet_influence_f64(const double* X, int64_t N, int64_t ld, int D,
+                             const double* mu, const double* B, const double* lin, double c0,
+                             double* psi, double* sums, void* ws, size_t ws_bytes, am_stream_t stream);
 /* B independent Frechet distances advancing together: every launch of the Newton-Schulz chain covers all B products (the set
  * index is a grid dimension), each set has its own state, stopping rule and stop code, and the workgroups of a set that has
  * stopped return at once.  Blocks of am_frechet_first_block() iterations are enqueued and `stream` is SYNCHRONISED once per
