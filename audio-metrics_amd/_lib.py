@@ -113,6 +113,11 @@ SIGNATURES = {
     "am_kmeans_update_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int]),
     "am_kmeans_update_f32": (c_int, [_P, c_int64, c_int64, c_int, _P, _P, _P, c_int64, _P, c_int64, _P, c_int64, _P, _P, c_size_t,
                                      _P]),
+    "am_sliced_project_f32": (c_int, [_P, c_int64, c_int64, _P, c_int64, c_int64, c_int, _P, c_int64, _P]),
+    "am_sort_rows_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "am_sort_rows_f32": (c_int, [_P, c_int64, c_int64, c_int64, _P, c_int64, _P, c_size_t, _P]),
+    "am_sliced_w_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
+    "am_sliced_w_f32": (c_int, [_P, c_int64, c_int64, _P, c_int64, c_int64, c_int64, c_int, _P, _P, _P, c_size_t, _P]),
     "am_knn_sym_eligible": (c_int, [c_int64, c_int, c_int]),
     "am_knn_list_width": (c_int, [c_int]),
     "am_knn_part_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),

@@ -1435,6 +1435,99 @@ def softmin(x, y, g=None, eps=None, prev=None, damping=0.0):
     return out, stats[0], stats[1]
 
 
+# ---- sliced Wasserstein distance: project, sort, transport cost (csrc/swd.hip) ----
+def sliced_project(x, theta):
+    """z[l, i] = <theta_l, x_i> for the rows of x [N, D] and the directions theta [L, D] (am_sliced_project_f32): float32
+    [L, N] as a device tensor, stream-ordered, nothing waits for the device.  A projection's bits do not depend on which
+    other directions share the call."""
+    if is_f64(x) or is_f64(theta):
+        raise NotImplementedError("sliced_project takes float32 rows (the float64 matrix-core form is not implemented)")
+    if x.dim() != 2 or theta.dim() != 2:
+        raise ValueError(f"rows and directions must be 2-D, got shapes {tuple(x.shape)} and {tuple(theta.shape)}")
+    if x.shape[1] != theta.shape[1]:
+        raise ValueError(f"feature widths differ: {x.shape[1]} and {theta.shape[1]}")
+    if x.shape[0] < 1 or theta.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError(f"sliced_project needs rows and directions (got shapes {tuple(x.shape)} and {tuple(theta.shape)})")
+    lib = _lib.load()
+    x, theta = as_matrix(x, "x"), as_matrix(theta, "theta")
+    dev = _same_device(x, theta)
+    n, d = x.shape
+    nl = theta.shape[0]
+    z = torch.empty((nl, n), dtype=torch.float32, device=dev)
+    _call(lib, "am_sliced_project_f32", dev, _ptr(x), n, _ld(x), _ptr(theta), nl, _ld(theta), d, _ptr(z), n)
+    return z
+
+
+def _sorted_matrix(z, name):
+    if is_f64(z):
+        raise NotImplementedError(f"{name} takes float32 rows (the float64 matrix-core form is not implemented)")
+    if not torch.is_tensor(z) or z.dim() != 2 or z.shape[0] < 1 or z.shape[1] < 1:
+        raise ValueError(f"{name} needs a 2-D tensor with rows and columns (got {tuple(getattr(z, 'shape', ()))})")
+
+
+def _unit_columns(z, name):
+    """float32, unit column stride, rows that do not overlap: what the key kernels address (any row stride >= columns)."""
+    _require_cuda(z, name)
+    if z.dtype != torch.float32 or z.stride(1) != 1 or (z.shape[0] > 1 and z.stride(0) < z.shape[1]):
+        z = z.to(torch.float32).contiguous()
+    return z
+
+
+def _row_stride(z):
+    return z.stride(0) if z.shape[0] > 1 else z.shape[1]
+
+
+def sort_rows(z, out=None):
+    """Every row of z [L, N] sorted ascending, keys only (am_sort_rows_f32): float32 [L, N] as a device tensor, stream-ordered,
+    nothing waits for the device.  -0.0 before +0.0, NaNs last as the canonical quiet NaN.  out=z sorts in place (z must then
+    be float32 with unit column stride); the workspace is one more [L, N] matrix."""
+    _sorted_matrix(z, "sort_rows")
+    lib = _lib.load()
+    src = _unit_columns(z, "z")
+    if out is None:
+        out = torch.empty(tuple(src.shape), dtype=torch.float32, device=src.device)
+    elif out is z:
+        if src is not z:
+            raise ValueError("sort_rows: an in-place sort needs a float32 tensor with unit column stride")
+    else:
+        raise ValueError("sort_rows: out must be None or z itself")
+    dev = src.device
+    nl, n = src.shape
+    nb = lib.am_sort_rows_workspace_bytes(nl, n)
+    ws = _workspace(nb, dev)
+    _call(lib, "am_sort_rows_f32", dev, _ptr(src), nl, n, _row_stride(src), _ptr(out), _row_stride(out), _ptr(ws), nb)
+    return out
+
+
+def sliced_w(zx_sorted, zy_sorted, p=2):
+    """W_p^p between row l of zx_sorted [L, n] and row l of zy_sorted [L, m], both sorted ascending, as uniform empirical
+    measures (am_sliced_w_f32): (w float64 [L], nonfinite int32 [L]) as device tensors, stream-ordered, nothing waits for the
+    device.  p is 1 or 2.  (zx, zy) and (zy, zx) return the same bits, a matrix against itself exactly 0.0; a row that holds
+    a NaN or an infinity on either side gives NaN and its count."""
+    _sorted_matrix(zx_sorted, "sliced_w")
+    _sorted_matrix(zy_sorted, "sliced_w")
+    if p not in (1, 2):
+        raise ValueError(f"p={p!r} must be 1 or 2")
+    if zx_sorted.shape[0] != zy_sorted.shape[0]:
+        raise ValueError(f"the two sides hold {zx_sorted.shape[0]} and {zy_sorted.shape[0]} projections")
+    n, m = int(zx_sorted.shape[1]), int(zy_sorted.shape[1])
+    if n * m >= 1 << 53:
+        raise ValueError(f"n * m = {n} * {m} must stay below 2^53 (the coupling's weights are exact integers)")
+    lib = _lib.load()
+    same = zx_sorted is zy_sorted
+    zx = _unit_columns(zx_sorted, "zx_sorted")
+    zy = zx if same else _unit_columns(zy_sorted, "zy_sorted")
+    dev = _same_device(zx, zy)
+    nl = zx.shape[0]
+    w = torch.empty(nl, dtype=torch.float64, device=dev)
+    bad = torch.empty(nl, dtype=torch.int32, device=dev)
+    nb = lib.am_sliced_w_workspace_bytes(nl, n, m)
+    ws = _workspace(nb, dev)
+    _call(lib, "am_sliced_w_f32", dev, _ptr(zx), n, _row_stride(zx), _ptr(zy), m, _row_stride(zy), nl, int(p), _ptr(w), _ptr(bad),
+          _ptr(ws), nb)
+    return w, bad
+
+
 # ---- partitioned symmetric k-NN (multi-GPU, every rank holds the full set) ----
 def knn_path(n, m, d, k, self_distance=True):
     """0 exact general kernel, 1 exact symmetric kernel, 2 / 3 f16 filter + exact verification (128 / 256-row engine)."""

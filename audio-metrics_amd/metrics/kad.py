@@ -42,6 +42,7 @@ class _ReferenceCache:
         self.vrow = {}             # gamma bits -> float64 [m] device tensor: the row sums v_j of Kyy (metrics/kad_stats.py)
         self.cells = {}            # (gamma bits, unit_rows) -> float64 [U, U] device tensor: the unit-pair sums of Kyy (metrics/kad_perm.py)
         self.sinkhorn = {}         # (blur, scaling, rtol, max_iter, diam2) -> the reference's own solve (metrics/sinkhorn.py)
+        self.sliced = {}           # (seed, n_projections) -> (chunk size, the sorted projections in chunks) (metrics/sliced.py)
 
 
 def reference_cache(y):

@@ -728,6 +728,41 @@ int am_psr_f32(const float* X, int64_t N, int64_t ldx, const float* Y, int64_t M
                void* ws, size_t ws_bytes, am_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * SLICED WASSERSTEIN distance, its three device steps (csrc/swd.hip)                 no counterpart in the reference
+ *   Every pointer below is a DEVICE pointer.  Everything is validated before the first HIP call; the calls are
+ *   asynchronous.  No floating-point atomics: two calls return the same bits.
+ *
+ *   PROJECT.  Z[l * ldz + i] = <Theta_l, x_i> for the N rows of X and the L rows of Theta, in f32 on the exact f32 tile
+ *   engine: the fmaf chain over the inner index in the engine's order (that of am_knn_search_f32's dot products), which
+ *   does not depend on the tile position - a projection has the same bits alone and among any other directions.  X, Theta
+ *   as for am_knn_search_f32 (16-byte aligned, ld % 4 == 0, ld >= D); ldz >= N, no alignment.  Elements of Z outside
+ *   [L][N] are not written.  No workspace.
+ *
+ *   SORT.  Every one of L rows of N floats (row stride ld_in) ascending into `out` (row stride ld_out), keys only.  An LSD
+ *   radix sort over u = b ^ (b >> 31 ? 0xffffffff : 0x80000000) of the bits b, 8 bits per pass, stable between passes; one
+ *   workgroup owns a row.  -0.0 sorts before +0.0; every NaN (either sign, any payload) comes last, behind +inf, and is
+ *   written as the quiet NaN 0x7fc00000; every other value keeps its bits.  out may be in (same pointer and stride);
+ *   elements between N and the row stride are neither read nor written.  1 <= N <= 2^31 - 1.  Workspace: one [L][N
+ *   rounded up to 4] float matrix.
+ *
+ *   W.  out[l] = W_p^p between the uniform empirical measures on row l of Zx (n atoms) and row l of Zy (m atoms), both
+ *   SORTED ascending (am_sort_rows_f32), p = 1 or 2, in f64: the quantile coupling on the merged grid {i / n} u {j / m},
+ *     out[l] = (1 / (n m)) sum over overlapping (i, j) of (min((i + 1) m, (j + 1) n) - max(i m, j n)) |x_(i) - y_(j)|^p
+ *   with integer weights (exact: n m < 2^53, else AM_ERR_BAD_SHAPE), one thread per atom of the larger side, f64 block sums
+ *   joined in a fixed tree.  The operands are ordered by (size, then argument order): (Zx, Zy) and (Zy, Zx) return the same
+ *   bits, a matrix against itself exactly 0.0.  nonfinite[l] (int32) = the number of NaNs and infinities in the two rows;
+ *   where it is not 0, out[l] is NaN.  Workspace: one (double, int) pair per 256 atoms of the larger side and row.
+ * ------------------------------------------------------------------------- */
+int am_sliced_project_f32(const float* X, int64_t N, int64_t ldx, const float* Theta, int64_t L, int64_t ldt, int D,
+                          float* Z, int64_t ldz, am_stream_t stream);
+size_t am_sort_rows_workspace_bytes(int64_t L, int64_t N);
+int am_sort_rows_f32(const float* in, int64_t L, int64_t N, int64_t ld_in, float* out, int64_t ld_out,
+                     void* ws, size_t ws_bytes, am_stream_t stream);
+size_t am_sliced_w_workspace_bytes(int64_t L, int64_t n, int64_t m);
+int am_sliced_w_f32(const float* Zx, int64_t n, int64_t ldzx, const float* Zy, int64_t m, int64_t ldzy, int64_t L, int p,
+                    double* out, int32_t* nonfinite, void* ws, size_t ws_bytes, am_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * A9, partitioned form for one-process-per-GPU callers that all hold the FULL set X.
  * The self-distance matrix is bitwise symmetric, so only half of the tile pairs are multiplied
  * (csrc/pairwise.hip, knn_sym_kernel); rank `part` of `nparts` owns a contiguous range of the 128-row blocks.

@@ -1,0 +1,50 @@
+"""The compile-time resources of csrc/swd.hip, as the shipped flags build it: both instantiations of the projection kernel
+(without / with the inner-dimension tail) keep two workgroups of four waves on a CU (at most 256 VGPRs, occupancy >= 2) and
+no kernel of the file - the projection, the sort, the transport cost and its finish - uses scratch memory."""
+import importlib.util
+import os
+import re
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "audio-metrics_amd", "csrc")
+
+
+@pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"), reason="hipcc not available")
+def test_projection_keeps_two_workgroups_per_cu_and_no_kernel_uses_scratch():
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    spec = importlib.util.spec_from_file_location("am_build", os.path.join(ROOT, "audio-metrics_amd", "_build.py"))
+    build = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(build)                                         # the flags the shipped library is built with
+    r = subprocess.run([hipcc, *build.HIPCC_FLAGS, "--cuda-device-only", "-c", "swd.hip", "-o", os.devnull,
+                        "-Rpass-analysis=kernel-resource-usage"], cwd=CSRC, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    usage, name = {}, None
+    for line in r.stderr.splitlines():
+        m = re.search(r"Function Name: (\S+)", line)
+        if m:
+            name = m.group(1)
+            usage[name] = {}
+        for key, short in (("ScratchSize \\[bytes/lane\\]", "scratch"), ("VGPRs", "vgprs"), ("Occupancy \\[waves/SIMD\\]", "occupancy")):
+            m = re.search(r"remark:\s+%s: (\d+)" % key, line)
+            if m and name:
+                usage[name][short] = int(m.group(1))
+    with open(os.path.join(CSRC, "swd.hip")) as f:
+        source = f.read()
+    declared = set(re.findall(r"^(\w+_kernel)\(", source, flags=re.M))
+    assert declared == {"sliced_project_kernel", "sort_rows_kernel", "sliced_w_kernel", "sliced_w_finish_kernel"}, declared
+    assert source.count("__global__") == len(declared)
+    assert "__launch_bounds__(ENGINE_THREADS, 2)" in source
+    tile = {n: u for n, u in usage.items() if "sliced_project_kernel" in n}
+    # the projection kernel without / with the inner-dimension tail
+    assert len(tile) == 2 and sum("ILb0E" in n for n in tile) == 1 and sum("ILb1E" in n for n in tile) == 1, sorted(tile)
+    # every __global__ kernel of the file: two projections, the sort, W at p = 1 and p = 2, its finish
+    assert len(usage) == 6 and all(any(k in n for n in usage) for k in declared), sorted(usage)
+    for n, u in usage.items():
+        print(n, u)
+        assert u["scratch"] == 0, (n, u)
+    for n, u in tile.items():
+        assert u["vgprs"] <= 256 and u["occupancy"] >= 2, (n, u)
