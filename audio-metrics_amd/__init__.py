@@ -28,6 +28,8 @@ from .metrics.pprecall import psr_radius, psr_by_group                        # 
 from .metrics.mauve import kmeans, mauve_score, mauve_from_histograms         # noqa: F401
 from .metrics.sinkhorn import sinkhorn_divergence, sinkhorn_schedule       # noqa: F401
 from .metrics.sliced import sliced_wasserstein_distance, sliced_directions   # noqa: F401
+from .metrics.classifier import (inception_score, inception_score_per_group, kl_divergence_paired,   # noqa: F401
+                                 paired_cosine_score)
 from .metrics.apa import apa, apa_compute_d_x_xp                              # noqa: F401
 from .metrics.vendi import vendi_score, vendi_score_per_group, vendi_from_eigenvalues   # noqa: F401
 

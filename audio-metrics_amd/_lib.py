@@ -118,6 +118,12 @@ SIGNATURES = {
     "am_sort_rows_f32": (c_int, [_P, c_int64, c_int64, c_int64, _P, c_int64, _P, c_size_t, _P]),
     "am_sliced_w_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
     "am_sliced_w_f32": (c_int, [_P, c_int64, c_int64, _P, c_int64, c_int64, c_int64, c_int, _P, _P, _P, c_size_t, _P]),
+    "am_class_groups_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
+    "am_class_groups_f32": (c_int, [_P, c_int64, c_int64, c_int, _P, _P, c_int, _P, _P, _P, c_size_t, _P]),
+    "am_class_groups_f64": (c_int, [_P, c_int64, c_int64, c_int, _P, _P, c_int, _P, _P, _P, c_size_t, _P]),
+    "am_row_pairs_workspace_bytes": (c_size_t, [c_int64]),
+    "am_row_pairs_f32": (c_int, [_P, c_int64, _P, c_int64, c_int64, c_int, c_int, c_double, _P, _P, _P, c_size_t, _P]),
+    "am_row_pairs_f64": (c_int, [_P, c_int64, _P, c_int64, c_int64, c_int, c_int, c_double, _P, _P, _P, c_size_t, _P]),
     "am_knn_sym_eligible": (c_int, [c_int64, c_int, c_int]),
     "am_knn_list_width": (c_int, [c_int]),
     "am_knn_part_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),

@@ -1528,6 +1528,95 @@ def sliced_w(zx_sorted, zy_sorted, p=2):
     return w, bad
 
 
+# ---- classifier-output scores: row quantities of logits, per group or per row pair (csrc/class_scores.hip) ----
+CLASS_GROUPS_MAX_COLUMNS = 2048                               # the column sums of a workgroup stay in LDS
+ROW_PAIRS_MAX_COLUMNS = 8192
+PAIR_MODES = {"cosine": 0, "kl_softmax": 1, "kl_sigmoid": 2, "kl_bernoulli": 3}      # enum am_pair_mode
+
+
+def check_score_rows(t, name, cap):
+    """The checks on a matrix of logits / embeddings that need no device: a 2-D float32 or float64 tensor with rows and
+    1 .. cap columns."""
+    if not torch.is_tensor(t) or t.dim() != 2:
+        raise ValueError(f"{name} must be a 2-D tensor, got shape {tuple(getattr(t, 'shape', ()))}")
+    if t.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"{name} must be float32 or float64, got {t.dtype}")
+    if t.shape[0] < 1 or not 1 <= t.shape[1] <= cap:
+        raise ValueError(f"{name} has shape {tuple(t.shape)}: it needs rows and 1 .. {cap} columns")
+
+
+def class_group_scores(rows, order, offsets, return_rows=False):
+    """The Inception Score terms of every group of rows of logits (am_class_groups_f32 / _f64, by the dtype of rows; the
+    group list as frechet_groups takes it, groups of any size >= 1; at most CLASS_GROUPS_MAX_COLUMNS columns).  Nothing
+    waits for the device: returns (rec, h, check) with rec the f64 device tensor [B, 4] of { mean of h over the group's rows,
+    m = sum pbar log pbar, log IS = mean h - m, non-finite rows } records (the first three NaN where the fourth is not 0), h
+    the f64 device tensor [n_total] of h = sum p log p per list position (None unless return_rows; NaN for a non-finite
+    row), and check() the one host read of the workspace's flag word, which raises ValueError for an index outside [0, N).
+    All arithmetic is f64: float32 rows and their float64 copies give the same bits, and so do two calls."""
+    check_score_rows(rows, "rows", CLASS_GROUPS_MAX_COLUMNS)
+    offs, b, host_offs = _group_offsets(offsets)
+    if order is None and offs[-1] > rows.shape[0]:
+        raise ValueError(f"no index list: offsets name {offs[-1]} stored rows, rows holds {rows.shape[0]}")
+    lib = _lib.load()
+    f64 = is_f64(rows)
+    rows = as_rows(rows, "rows")
+    n, c = rows.shape
+    dev = rows.device
+    idx = _group_index(order, offs[-1], rows)
+    rec = torch.empty((b, 4), dtype=torch.float64, device=dev)
+    h = torch.empty(offs[-1], dtype=torch.float64, device=dev) if return_rows else None
+    nb = lib.am_class_groups_workspace_bytes(offs[-1], b, c)
+    ws = _workspace(nb, dev)
+    _call(lib, "am_class_groups_f64" if f64 else "am_class_groups_f32", dev, _ptr(rows), n, _ld64(rows) if f64 else _ld(rows), c,
+          _ptr(idx) if idx is not None else ctypes.c_void_p(None), ctypes.cast(host_offs, ctypes.c_void_p), b, _ptr(rec),
+          _ptr(h) if h is not None else ctypes.c_void_p(None), _ptr(ws), nb)
+    return rec, h, _index_check(ws, idx, n, "group rows")
+
+
+def check_row_pair(a, b, mode, eps):
+    """Everything row_pair_scores checks, without a device call; returns eps as a float."""
+    if mode not in PAIR_MODES:
+        raise ValueError(f"mode={mode!r} must be one of {sorted(PAIR_MODES)}")
+    try:
+        eps = float(eps)
+    except (TypeError, ValueError):
+        raise ValueError(f"eps={eps!r} must be a finite number >= 0") from None
+    if not (math.isfinite(eps) and eps >= 0.0):
+        raise ValueError(f"eps={eps!r} must be a finite number >= 0")
+    check_score_rows(a, "a", ROW_PAIRS_MAX_COLUMNS)
+    check_score_rows(b, "b", ROW_PAIRS_MAX_COLUMNS)
+    if a.dtype != b.dtype:
+        raise NotImplementedError(f"the two sides must have one dtype, got {a.dtype} and {b.dtype} (convert one of them)")
+    if tuple(a.shape) != tuple(b.shape):
+        raise ValueError(f"the rows are paired one to one: shapes {tuple(a.shape)} and {tuple(b.shape)} differ")
+    return eps
+
+
+def row_pair_scores(a, b, mode, eps=0.0, return_rows=False):
+    """One value per row pair (a_i, b_i) of two matrices of equal shape and dtype (am_row_pairs_f32 / _f64): mode "cosine",
+    or "kl_softmax" / "kl_sigmoid" / "kl_bernoulli" with a the candidate's logits and b the reference's (eps >= 0 is added
+    inside the candidate's logarithm).  Returns (sums, rows): sums the f64 device tensor [4] = { sum v, sum v^2, finite rows,
+    non-finite rows } (a value that is not finite is counted and left out of the sums), rows the f64 device tensor [N] of the
+    values, or None unless return_rows.  Stream-ordered, nothing waits for the device; all arithmetic is f64 and every sum
+    has a fixed order."""
+    eps = check_row_pair(a, b, mode, eps)
+    lib = _lib.load()
+    f64 = is_f64(a)
+    same = a is b
+    a = as_rows(a, "a")
+    b = a if same else as_rows(b, "b")
+    dev = _same_device(a, b)
+    n, c = a.shape
+    sums = torch.empty(4, dtype=torch.float64, device=dev)
+    rows = torch.empty(n, dtype=torch.float64, device=dev) if return_rows else None
+    nb = lib.am_row_pairs_workspace_bytes(n)
+    ws = _workspace(nb, dev)
+    ld = _ld64 if f64 else _ld
+    _call(lib, "am_row_pairs_f64" if f64 else "am_row_pairs_f32", dev, _ptr(a), ld(a), _ptr(b), ld(b), n, c, PAIR_MODES[mode], eps,
+          _ptr(rows) if rows is not None else ctypes.c_void_p(None), _ptr(sums), _ptr(ws), nb)
+    return sums, rows
+
+
 # ---- partitioned symmetric k-NN (multi-GPU, every rank holds the full set) ----
 def knn_path(n, m, d, k, self_distance=True):
     """0 exact general kernel, 1 exact symmetric kernel, 2 / 3 f16 filter + exact verification (128 / 256-row engine)."""

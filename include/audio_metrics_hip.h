@@ -763,6 +763,58 @@ int am_sliced_w_f32(const float* Zx, int64_t n, int64_t ldzx, const float* Zy, i
                     double* out, int32_t* nonfinite, void* ws, size_t ws_bytes, am_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * CLASSIFIER-OUTPUT scores: row-wise on logits (csrc/class_scores.hip)               no counterpart in the reference
+ *   Every pointer below is a DEVICE pointer except `offsets`.  Everything is validated before the first HIP call; the
+ *   calls are asynchronous.  All arithmetic is f64: float32 rows are converted on load (exact), so the _f32 and _f64
+ *   entry points return the SAME BITS on the same values.  No floating-point atomics; every sum runs in an order that
+ *   depends on the shapes and the group sizes only: two calls return the same bits.
+ *
+ *   Row quantities of a row l of C logits: M = max l_c, e_c = exp(l_c - M), S = sum e_c, U = sum e_c (l_c - M),
+ *   p_c = e_c / S, h = sum p_c log p_c = U / S - log S.  A logit of -inf is a masked class (p_c = 0, no term in U).  A
+ *   row with a NaN, a +inf, or nothing but -inf is NON-FINITE: its h is NaN and it is counted.
+ *
+ *   CLASS GROUPS.  Group b = the rows L[idx[offsets[b] + j]] (the group list of am_stats_gather_*; idx == NULL: the rows
+ *   in stored order; offsets: HOST, B + 1 entries from 0, every group >= 1 rows of any number).  With n_b rows,
+ *     pbar_c = (1 / n_b) sum_i p_ic,   m_b = sum_c pbar_c log pbar_c (0 log 0 = 0),   log IS_b = (1 / n_b) sum_i h_i - m_b
+ *   out_rec[b] = { (1 / n_b) sum h, m_b, log IS_b, non-finite rows of the group } (4 doubles; the first three NaN where
+ *   the fourth is not 0); out_h (may be NULL) [offsets[B]]: h per list position.  The list positions of a group are cut
+ *   into segments of 64 (a segment never crosses a group), one workgroup per segment, a wave per row, the rows of a wave
+ *   in ascending order, the four waves' column sums added in wave order, a group's segments in ascending order, m_b in a
+ *   fixed tree: the bits of a group depend on its rows and their list order alone - not on idx being NULL or not, not on
+ *   the other groups.  The workspace opens with the flag word of the group-list protocol (1 + the list position of an
+ *   index outside [0, N), or 0; such an index is never dereferenced and its row counts as non-finite).
+ *   Limits: 1 <= C <= 2048 (the column sums of a workgroup stay in LDS), N, B >= 1, else AM_ERR_BAD_SHAPE; L as for
+ *   am_stats_gather_* (float32: 16-byte aligned, ld % 4 == 0, N * ld < 2^30; ld >= C), else AM_ERR_BAD_ARG / _BAD_SHAPE.
+ *
+ *   ROW PAIRS.  One value v_i per row i of two [N, C] matrices (cand, ref) with their own leading dimensions:
+ *     AM_PAIR_COSINE        <a, b> / sqrt(|a|^2 |b|^2); a zero norm gives NaN
+ *     AM_PAIR_KL_SOFTMAX    sum_c p^r_c (log p^r_c - log(p^c_c + eps)), p = softmax of the row; at eps == 0 evaluated as
+ *                           sum_c p^r_c ((r_c - lse_r) - (c_c - lse_c)); terms with p^r_c = 0 are 0; a non-finite row on
+ *                           either side gives NaN
+ *     AM_PAIR_KL_SIGMOID    sum_c s(r_c) (log s(r_c) - log(s(c_c) + eps)), s the logistic function (one-term form: not a
+ *                           divergence, may be negative)
+ *     AM_PAIR_KL_BERNOULLI  sum_c [ s log(s / (t + eps)) + (1 - s) log((1 - s) / (1 - t + eps)) ], s = s(r_c), t = s(c_c)
+ *   (at eps == 0 the sigmoid forms use log s(x) = min(x, 0) - log1p(exp(-|x|)), log(1 - s(x)) = log s(-x)).
+ *   rows_out (may be NULL) [N] = v; sums[4] = { sum v, sum v^2, finite rows, non-finite rows }, a value that is not
+ *   finite being counted and left out of the two sums.  One wave per pair, a workgroup the rows [64 g, 64 g + 64): its
+ *   four sums by an xor butterfly over the 64 values, the workgroups' partials thread-strided (w = t, t + 256, ...), an xor
+ *   butterfly per wave, then (wave 0 + wave 1) + (wave 2 + wave 3).
+ *   Limits: N >= 1, 1 <= C <= 8192, else AM_ERR_BAD_SHAPE; ld >= C, float32 rows 16-byte aligned with ld % 4 == 0, a
+ *   known mode, eps finite and >= 0, else AM_ERR_BAD_ARG.
+ * ------------------------------------------------------------------------- */
+enum am_pair_mode { AM_PAIR_COSINE = 0, AM_PAIR_KL_SOFTMAX = 1, AM_PAIR_KL_SIGMOID = 2, AM_PAIR_KL_BERNOULLI = 3 };
+size_t am_class_groups_workspace_bytes(int64_t n_total, int B, int C);
+int am_class_groups_f32(const float* L, int64_t N, int64_t ld, int C, const int64_t* idx, const int64_t* offsets, int B,
+                        double* out_rec, double* out_h, void* ws, size_t ws_bytes, am_stream_t stream);
+int am_class_groups_f64(const double* L, int64_t N, int64_t ld, int C, const int64_t* idx, const int64_t* offsets, int B,
+                        double* out_rec, double* out_h, void* ws, size_t ws_bytes, am_stream_t stream);
+size_t am_row_pairs_workspace_bytes(int64_t N);
+int am_row_pairs_f32(const float* cand, int64_t ldc, const float* ref, int64_t ldr, int64_t N, int C, int mode, double eps,
+                     double* rows_out, double* sums, void* ws, size_t ws_bytes, am_stream_t stream);
+int am_row_pairs_f64(const double* cand, int64_t ldc, const double* ref, int64_t ldr, int64_t N, int C, int mode, double eps,
+                     double* rows_out, double* sums, void* ws, size_t ws_bytes, am_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * A9, partitioned form for one-process-per-GPU callers that all hold the FULL set X.
  * The self-distance matrix is bitwise symmetric, so only half of the tile pairs are multiplied
  * (csrc/pairwise.hip, knn_sym_kernel); rank `part` of `nparts` owns a contiguous range of the 128-row blocks.
