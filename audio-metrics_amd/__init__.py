@@ -32,6 +32,8 @@ from .metrics.classifier import (inception_score, inception_score_per_group, kl_
                                  paired_cosine_score)
 from .metrics.apa import apa, apa_compute_d_x_xp                              # noqa: F401
 from .metrics.vendi import vendi_score, vendi_score_per_group, vendi_from_eigenvalues   # noqa: F401
+from .metrics.fkea import (vendi_score_rff, rke_score, kernel_novelty_score, rff_frequencies,   # noqa: F401
+                           novelty_from_eigenvalues)
 
 from .embed import ItemCategory, embedding_pipeline                            # noqa: F401
 from .projection import IncrementalPCA                                         # noqa: F401

@@ -118,6 +118,13 @@ SIGNATURES = {
     "am_sort_rows_f32": (c_int, [_P, c_int64, c_int64, c_int64, _P, c_int64, _P, c_size_t, _P]),
     "am_sliced_w_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
     "am_sliced_w_f32": (c_int, [_P, c_int64, c_int64, _P, c_int64, c_int64, c_int64, c_int, _P, _P, _P, c_size_t, _P]),
+    "am_rff_max_features": (c_int, []),
+    "am_rff_features_workspace_bytes": (c_size_t, [c_int64]),
+    "am_rff_features_f32": (c_int, [_P, c_int64, c_int64, c_int, _P, c_int, c_int64, c_int64, c_int64, c_double, _P, _P, c_int64, _P,
+                                    c_size_t, _P]),
+    "am_rff_moment_chunks": (c_int, [c_int64, c_int]),
+    "am_rff_moment_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
+    "am_rff_moment_f32": (c_int, [_P, c_int64, c_int64, c_int, _P, c_int, c_int64, c_double, _P, _P, _P, c_size_t, _P]),
     "am_class_groups_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
     "am_class_groups_f32": (c_int, [_P, c_int64, c_int64, c_int, _P, _P, c_int, _P, _P, _P, c_size_t, _P]),
     "am_class_groups_f64": (c_int, [_P, c_int64, c_int64, c_int, _P, _P, c_int, _P, _P, _P, c_size_t, _P]),

@@ -1528,6 +1528,113 @@ def sliced_w(zx_sorted, zy_sorted, p=2):
     return w, bad
 
 
+# ---- random Fourier features of the Gaussian kernel and their moment matrix (csrc/rff.hip) ----
+_RFF_CAPS = {}
+
+
+def rff_max_features():
+    if "features" not in _RFF_CAPS:
+        _RFF_CAPS["features"] = int(_lib.load().am_rff_max_features())
+    return _RFF_CAPS["features"]
+
+
+def rff_moment_chunks(n, n_features):
+    """The number of row chunks am_rff_moment_f32 folds for n rows and n_features frequencies (a host query)."""
+    return int(_lib.load().am_rff_moment_chunks(int(n), int(n_features)))
+
+
+def _rff_width_args(bw2, inv_bw):
+    """The (inv_bw, bw2 pointer) arguments of the am_rff_* entry points from exactly one of a float32 device scalar holding a
+    squared bandwidth and the number 1 / bandwidth; no device call."""
+    if (bw2 is None) == (inv_bw is None):
+        raise ValueError("exactly one of bw2 (device scalar) and inv_bw (number) must be given")
+    if bw2 is None:
+        inv_bw = float(inv_bw)
+        if not (inv_bw > 0.0 and inv_bw < float("inf")):
+            raise ValueError(f"inv_bw={inv_bw!r} must be a finite positive number")
+        return inv_bw, ctypes.c_void_p(None)
+    _require_cuda(bw2, "bw2")
+    if bw2.dtype != torch.float32 or bw2.numel() != 1:
+        raise ValueError("bw2 must be a float32 device scalar")
+    return 0.0, _ptr(bw2)
+
+
+def _rff_check_inputs(what, x, w):
+    if is_f64(x) or is_f64(w):
+        raise NotImplementedError(f"{what} takes float32 rows (the float64 matrix-core form is not implemented)")
+    if x.dim() != 2 or w.dim() != 2:
+        raise ValueError(f"rows and frequencies must be 2-D, got shapes {tuple(x.shape)} and {tuple(w.shape)}")
+    if x.shape[1] != w.shape[1]:
+        raise ValueError(f"feature widths differ: {x.shape[1]} and {w.shape[1]}")
+    if x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError(f"{what} needs rows (got shape {tuple(x.shape)})")
+    if not 1 <= w.shape[0] <= rff_max_features():
+        raise ValueError(f"{what} takes 1 .. {rff_max_features()} frequencies, got {w.shape[0]}")
+
+
+def _rff_count_check(ws):
+    """check() of the am_rff_* calls: the one host read of the int64 at the head of the workspace - the number of rows with
+    a NaN or an infinity (their features are zeros)."""
+    def check():
+        return int(ws[:8].view(torch.int64).item())
+    return check
+
+
+def rff_features(x, w, bw2=None, inv_bw=None, row0=0, nrows=None, out=None, return_check=False):
+    """The random Fourier features of rows [row0, row0 + nrows) of x [N, D] under the frequencies w [R, D]
+    (am_rff_features_f32): the float64 device tensor f [2R, nrows], feature-major, f[l, i] = cos(a) / sqrt(R) and f[R + l, i] =
+    sin(a) / sqrt(R) with a = (double) <w_l, x_(row0 + i)> * inv_bw - `inv_bw` a number, or `bw2` a float32 DEVICE scalar
+    holding bw^2 (inv_bw = 1 / sqrt(bw2) is formed on the device, no host round trip).  Stream-ordered, nothing waits for the
+    device.  A feature's bits depend neither on the other frequencies of the call nor on (row0, nrows); a row with a NaN or
+    an infinity gives zeros.  out: a contiguous float64 [2R, ldo >= nrows] device tensor to write into (columns from nrows on
+    are left as they are; it is returned as it is).  return_check=True: (f, check), check() the one host read of the number
+    of non-finite rows."""
+    _rff_check_inputs("rff_features", x, w)
+    inv_arg, dev_arg = _rff_width_args(bw2, inv_bw)
+    n_all = int(x.shape[0])
+    row0 = int(row0)
+    nrows = n_all - row0 if nrows is None else int(nrows)
+    if row0 < 0 or nrows < 1 or row0 + nrows > n_all:
+        raise ValueError(f"rows [{row0}, {row0} + {nrows}) are not inside [0, {n_all})")
+    r = int(w.shape[0])
+    if out is not None and (not torch.is_tensor(out) or out.dtype != torch.float64 or out.dim() != 2 or out.shape[0] != 2 * r
+                            or out.shape[1] < nrows or not out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous float64 [2R = {2 * r}, >= {nrows}] device tensor")
+    lib = _lib.load()
+    x, w = as_matrix(x, "x"), as_matrix(w, "w")
+    dev = _same_device(x, w) if out is None else _same_device(x, w, out)
+    if bw2 is not None:
+        _same_device(x, bw2)
+    d = x.shape[1]
+    f = torch.empty((2 * r, nrows), dtype=torch.float64, device=dev) if out is None else out
+    nb = lib.am_rff_features_workspace_bytes(nrows)
+    ws = _workspace(nb, dev)
+    _call(lib, "am_rff_features_f32", dev, _ptr(x), n_all, _ld(x), d, _ptr(w), r, _ld(w), row0, nrows, inv_arg, dev_arg, _ptr(f),
+          int(f.shape[1]), _ptr(ws), nb)
+    return (f, _rff_count_check(ws)) if return_check else f
+
+
+def rff_moment(x, w, bw2=None, inv_bw=None):
+    """S = (1 / n) sum_i phi_i phi_i^T over all rows of x, phi_i the random Fourier features rff_features describes, as an f64
+    device tensor [2R, 2R] (am_rff_moment_f32): exactly symmetric, trace 1; its non-zero eigenvalues approximate those of the
+    Gaussian kernel's K / n.  Returns (s, check); nothing waits for the device.  check() is the one host read of the number
+    of rows with a NaN or an infinity (they count as zeros in s)."""
+    _rff_check_inputs("rff_moment", x, w)
+    inv_arg, dev_arg = _rff_width_args(bw2, inv_bw)
+    lib = _lib.load()
+    x, w = as_matrix(x, "x"), as_matrix(w, "w")
+    dev = _same_device(x, w)
+    if bw2 is not None:
+        _same_device(x, bw2)
+    n, d = x.shape
+    r = int(w.shape[0])
+    s = torch.empty((2 * r, 2 * r), dtype=torch.float64, device=dev)
+    nb = lib.am_rff_moment_workspace_bytes(n, d, r)
+    ws = _workspace(nb, dev)
+    _call(lib, "am_rff_moment_f32", dev, _ptr(x), n, _ld(x), d, _ptr(w), r, _ld(w), inv_arg, dev_arg, _ptr(s), _ptr(ws), nb)
+    return s, _rff_count_check(ws)
+
+
 # ---- classifier-output scores: row quantities of logits, per group or per row pair (csrc/class_scores.hip) ----
 CLASS_GROUPS_MAX_COLUMNS = 2048                               # the column sums of a workgroup stay in LDS
 ROW_PAIRS_MAX_COLUMNS = 8192

@@ -43,6 +43,7 @@ class _ReferenceCache:
         self.cells = {}            # (gamma bits, unit_rows) -> float64 [U, U] device tensor: the unit-pair sums of Kyy (metrics/kad_perm.py)
         self.sinkhorn = {}         # (blur, scaling, rtol, max_iter, diam2) -> the reference's own solve (metrics/sinkhorn.py)
         self.sliced = {}           # (seed, n_projections) -> (chunk size, the sorted projections in chunks) (metrics/sliced.py)
+        self.rff = {}              # (bandwidth source, n_features, seed) -> float64 [2R, 2R] device tensor: the moment matrix S (metrics/fkea.py)
 
 
 def reference_cache(y):

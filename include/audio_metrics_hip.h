@@ -763,6 +763,48 @@ int am_sliced_w_f32(const float* Zx, int64_t n, int64_t ldzx, const float* Zy, i
                     double* out, int32_t* nonfinite, void* ws, size_t ws_bytes, am_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * RANDOM FOURIER FEATURES of the Gaussian kernel and their moment matrix (csrc/rff.hip)   no counterpart in the reference
+ *   FKEA (Ospanov, Zhang, Jalali, Cao, Bogdanov, Farnia, NeurIPS 2024): the spectrum of K / n, K_ij = exp(-|x_i - x_j|^2 /
+ *   (2 bw^2)), at any number of rows from a [2R][2R] matrix.  Every pointer below is a DEVICE pointer.  Everything is
+ *   validated before the first HIP call; the calls are asynchronous.  No floating-point atomics: two calls return the same
+ *   bits.
+ *
+ *   W [R][D] float32: the frequencies, a UNIT-bandwidth standard normal draw (the package draws
+ *     numpy.random.default_rng(seed).standard_normal((R, D)) rounded to float32 once), independent of the bandwidth.
+ *   z_il = <w_l, x_i> in f32 on the exact f32 tile engine (the fmaf chain of am_sliced_project_f32: the bits do not depend on
+ *     the tile position).  a_il = (double) z_il * inv_bw with inv_bw = 1 / bw in f64: the host double `inv_bw` (finite, > 0),
+ *     or, with bw2_dev != NULL (a float32 DEVICE scalar holding a median squared distance, the output of
+ *     am_pairwise_select_f32), 1 / sqrt((double) *bw2_dev) formed on the device - no host round trip.
+ *   phi_i = R^(-1/2) [cos a_i1 .. cos a_iR, sin a_i1 .. sin a_iR], cos and sin in f64 (|error| < 2^-53; an argument of
+ *     magnitude >= 2^30 - whose float32 projection has no phase left - gives NaN).  <phi_i, phi_j> is an unbiased estimate
+ *     of K_ij and |phi_i|^2 = 1.
+ *   S = (1 / n) sum_i phi_i phi_i^T, [2R][2R] f64, trace 1: its non-zero eigenvalues are those of Phi Phi^T / n, which
+ *     approximates K / n with a Monte-Carlo error of order 1 / sqrt(R).
+ *
+ *   FEATURES.  F[l * ldo + i] = cos(a)/sqrt(R) and F[(R + l) * ldo + i] = sin(a)/sqrt(R) for the rows row0 + i, 0 <= i <
+ *   nrows, of X: feature-major, ldo >= nrows.  A feature has the same bits alone and among any other frequencies, and for
+ *   every (row0, nrows) that covers its row.  Elements with i >= nrows are not written.  A row with a NaN or an infinity
+ *   writes zeros and is counted: `ws` opens with ONE int64, the number of such rows in [row0, row0 + nrows).  X, W as for
+ *   am_sliced_project_f32 (16-byte aligned, ld % 4 == 0, ld >= D); 1 <= R <= am_rff_max_features() = 1024.
+ *
+ *   MOMENT.  out_s [2R][2R] = S over all N rows.  The rows are cut into am_rff_moment_chunks(N, R) chunks of 4096; per chunk
+ *   the features go to the workspace and their Gram runs on v_mfma_f64_16x16x4_f64 over the upper 64 x 64 tiles, the chunk's
+ *   rows split among workgroups whose partial tiles are added in split order, chunk after chunk in stream order; the last
+ *   fold divides by N and writes the mirror, so S is exactly symmetric.  `ws` opens with the same int64 count, over all N
+ *   rows (their features are zeros and the divisor stays N: N S is the sum over the finite rows).  The workspace holds one
+ *   chunk - it does not grow with N past 4096 rows.
+ * ------------------------------------------------------------------------- */
+int am_rff_max_features(void);
+size_t am_rff_features_workspace_bytes(int64_t nrows);
+int am_rff_features_f32(const float* X, int64_t N, int64_t ldx, int D, const float* W, int R, int64_t ldw,
+                        int64_t row0, int64_t nrows, double inv_bw, const float* bw2_dev,
+                        double* F, int64_t ldo, void* ws, size_t ws_bytes, am_stream_t stream);
+int am_rff_moment_chunks(int64_t n, int R);
+size_t am_rff_moment_workspace_bytes(int64_t n, int D, int R);
+int am_rff_moment_f32(const float* X, int64_t N, int64_t ldx, int D, const float* W, int R, int64_t ldw,
+                      double inv_bw, const float* bw2_dev, double* out_s, void* ws, size_t ws_bytes, am_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * CLASSIFIER-OUTPUT scores: row-wise on logits (csrc/class_scores.hip)               no counterpart in the reference
  *   Every pointer below is a DEVICE pointer except `offsets`.  Everything is validated before the first HIP call; the
  *   calls are asynchronous.  All arithmetic is f64: float32 rows are converted on load (exact), so the _f32 and _f64
