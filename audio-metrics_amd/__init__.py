@@ -34,6 +34,8 @@ from .metrics.apa import apa, apa_compute_d_x_xp                              # 
 from .metrics.vendi import vendi_score, vendi_score_per_group, vendi_from_eigenvalues   # noqa: F401
 from .metrics.fkea import (vendi_score_rff, rke_score, kernel_novelty_score, rff_frequencies,   # noqa: F401
                            novelty_from_eigenvalues)
+from .metrics.fld import (feature_likelihood_divergence, feature_likelihood_fit, fld_adam_step,   # noqa: F401
+                          fld_from_logliks, authenticity_score)
 
 from .embed import ItemCategory, embedding_pipeline                            # noqa: F401
 from .projection import IncrementalPCA                                         # noqa: F401

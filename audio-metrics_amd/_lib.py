@@ -103,6 +103,11 @@ SIGNATURES = {
     "am_softmin_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int]),
     "am_softmin_f32": (c_int, [_P, c_int64, c_int64, _P, c_int64, c_int64, c_int, _P, c_double, _P, c_double, _P, _P, _P, c_size_t,
                                _P]),
+    "am_fld_loglik_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int]),
+    "am_fld_loglik_f32": (c_int, [_P, c_int64, c_int64, _P, c_int64, c_int64, c_int, _P, _P, _P, _P, c_size_t, _P]),
+    "am_fld_grad_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int]),
+    "am_fld_grad_f32": (c_int, [_P, c_int64, c_int64, _P, c_int64, c_int64, c_int, _P, _P, _P, _P, _P, c_int64, c_double, c_double,
+                                _P, _P, _P, _P, c_size_t, _P]),
     "am_sample_scores_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int]),
     "am_sample_scores_chunks": (c_int, [c_int64, c_int64, c_int]),
     "am_sample_scores_f32": (c_int, [_P, c_int64, c_int64, _P, c_int64, c_int64, c_int, _P, _P, _P, _P, _P, _P, _P, c_size_t,

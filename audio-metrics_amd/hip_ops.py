@@ -1435,6 +1435,97 @@ def softmin(x, y, g=None, eps=None, prev=None, damping=0.0):
     return out, stats[0], stats[1]
 
 
+# ---- feature likelihood of a mixture of isotropic Gaussians: the loglik sweep and the gradient sweep (csrc/fld.hip) ----
+FLD_THETA_MAX = 30.0                                   # upper clamp of theta = log sigma^2 (csrc/fld.hip: THETA_MAX)
+FLD_THETA_MIN_LIMIT = -math.log(2.0 * 3.4028234663852886e38)      # below it 0.5 exp(-theta) is no finite float32 number
+
+
+def _fld_vector_ok(t, rows):
+    return torch.is_tensor(t) and t.dim() == 1 and t.shape[0] == rows and t.dtype == torch.float64
+
+
+def _fld_matrices(x, g, name):
+    if is_f64(x) or is_f64(g):
+        raise NotImplementedError(f"{name} takes float32 rows (the float64 matrix-core form is not implemented)")
+    if x.dim() != 2 or g.dim() != 2:
+        raise ValueError(f"x and g must be 2-D, got shapes {tuple(x.shape)} and {tuple(g.shape)}")
+    if x.shape[1] != g.shape[1]:
+        raise ValueError(f"feature widths differ: {x.shape[1]} and {g.shape[1]}")
+    if x.shape[0] < 1 or g.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError(f"{name} needs rows on both sides (got shapes {tuple(x.shape)} and {tuple(g.shape)})")
+
+
+def fld_loglik(x, g, theta, stats=None):
+    """l_i = logsumexp_j (-h_j d2(x_i, g_j) - c_j) - log M - (D / 2) log 2 pi for every row of x under the mixture of
+    isotropic Gaussians on the M rows of g with log-variances theta (float64 [M]; h = 0.5 exp(-theta), c = (D / 2) theta)
+    (am_fld_loglik_f32): (loglik float64 [N], stats float64 [3] = {sum of the finite l, rows with a finite l, rows without})
+    as device tensors, stream-ordered, nothing waits for the device.  `stats`: a contiguous float64 [3] device tensor to
+    write the three numbers into (a row of a fit's history).  The squared distances have the bits of
+    knn_search(x, g, ., squared=True); a row with a non-finite element has l = -inf, a centre with one contributes 0.  Two
+    calls return the same bits."""
+    _fld_matrices(x, g, "fld_loglik")
+    if not _fld_vector_ok(theta, g.shape[0]):
+        raise ValueError(f"theta must be a float64 tensor with one log-variance per row of g ({g.shape[0]})")
+    if stats is not None and not (_fld_vector_ok(stats, 3) and stats.is_contiguous()):
+        raise ValueError("stats must be a contiguous float64 tensor of 3 elements")
+    lib = _lib.load()
+    x, g = as_matrix(x, "x"), as_matrix(g, "g")
+    _require_cuda(theta, "theta")
+    theta = theta.contiguous()
+    if stats is not None:
+        _require_cuda(stats, "stats")
+    dev = _same_device(x, g, theta, *(() if stats is None else (stats,)))
+    n, d = x.shape
+    m = g.shape[0]
+    out = torch.empty(n, dtype=torch.float64, device=dev)
+    if stats is None:
+        stats = torch.empty(3, dtype=torch.float64, device=dev)
+    nb = lib.am_fld_loglik_workspace_bytes(n, m, d)
+    ws = _workspace(nb, dev)
+    _call(lib, "am_fld_loglik_f32", dev, _ptr(x), n, _ld(x), _ptr(g), m, _ld(g), d, _ptr(theta), _ptr(out), _ptr(stats), _ptr(ws), nb)
+    return out, stats
+
+
+def fld_grad_step(g, x, theta, lse, n_finite, m, v, step, lr, theta_min):
+    """One full-batch Adam step on the log-variances theta of the mixture on the rows of g, fitted to the rows of x
+    (am_fld_grad_f32): (theta, m, v, A, B), new float64 [M] device tensors, stream-ordered, nothing waits for the device - the
+    arguments are left as they are.  lse: float64 [N], the loglik of fld_loglik(x, g, theta); n_finite: a float64 device
+    tensor of one element, its stats[1].  A_j = sum_i r_ij and B_j = sum_i r_ij d2_ij over the responsibilities r_ij; the
+    gradient is -(h_j B_j - (D / 2) A_j) / n_finite and the update that of metrics.fld.fld_adam_step with step >= 1, clamped
+    to [theta_min, 30].  Two calls return the same bits."""
+    _fld_matrices(x, g, "fld_grad_step")
+    for t, name, rows in ((theta, "theta", g.shape[0]), (m, "m", g.shape[0]), (v, "v", g.shape[0]), (lse, "lse", x.shape[0])):
+        if not _fld_vector_ok(t, rows):
+            raise ValueError(f"{name} must be a float64 tensor of {rows} elements")
+    if not (torch.is_tensor(n_finite) and n_finite.dtype == torch.float64 and n_finite.numel() == 1):
+        raise ValueError("n_finite must be a float64 tensor of one element (stats[1] of fld_loglik)")
+    step, lr, theta_min = int(step), float(lr), float(theta_min)
+    if step < 1:
+        raise ValueError(f"step={step} must be at least 1")
+    if not math.isfinite(lr) or lr < 0.0:
+        raise ValueError(f"lr={lr!r} must be finite and not negative")
+    if not math.isfinite(theta_min) or not FLD_THETA_MIN_LIMIT <= theta_min <= FLD_THETA_MAX:
+        raise ValueError(f"theta_min={theta_min!r} must lie in [{FLD_THETA_MIN_LIMIT:.4f}, {FLD_THETA_MAX}]: "
+                         "0.5 exp(-theta) has to stay a normal float32 number")
+    lib = _lib.load()
+    g, x = as_matrix(g, "g"), as_matrix(x, "x")
+    vectors = []
+    for t, name in ((theta, "theta"), (lse, "lse"), (n_finite, "n_finite"), (m, "m"), (v, "v")):
+        _require_cuda(t, name)
+        vectors.append(t.contiguous())
+    theta, lse, n_finite = vectors[:3]
+    dev = _same_device(g, x, *vectors)
+    m, v = vectors[3].clone(), vectors[4].clone()                    # the kernel updates its moments in place
+    rows, d = g.shape
+    n = x.shape[0]
+    theta_out, a, b = (torch.empty(rows, dtype=torch.float64, device=dev) for _ in range(3))
+    nb = lib.am_fld_grad_workspace_bytes(rows, n, d)
+    ws = _workspace(nb, dev)
+    _call(lib, "am_fld_grad_f32", dev, _ptr(g), rows, _ld(g), _ptr(x), n, _ld(x), d, _ptr(theta), _ptr(lse), _ptr(n_finite), _ptr(m),
+          _ptr(v), step, lr, theta_min, _ptr(theta_out), _ptr(a), _ptr(b), _ptr(ws), nb)
+    return theta_out, m, v, a, b
+
+
 # ---- sliced Wasserstein distance: project, sort, transport cost (csrc/swd.hip) ----
 def sliced_project(x, theta):
     """z[l, i] = <theta_l, x_i> for the rows of x [N, D] and the directions theta [L, D] (am_sliced_project_f32): float32

@@ -667,6 +667,52 @@ int am_softmin_f32(const float* X, int64_t N, int64_t ldx, const float* Y, int64
                    void* ws, size_t ws_bytes, am_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * FEATURE LIKELIHOOD of a mixture of isotropic Gaussians on the rows of G (csrc/fld.hip)   no counterpart in the reference
+ *   The two sweeps of the feature likelihood divergence (Jiralerspong et al., NeurIPS 2023).  G: the M centres, theta:
+ *   DEVICE double[M], theta_j = log sigma_j^2; h_j = 0.5 exp(-theta_j) and c_j = (D / 2) theta_j are rounded to f32 once per
+ *   call.  Per pair, in f32 on the exact f32 tile engine, no N x M matrix in either direction:
+ *     d2   = max(fmaf(-2, <x_i, g_j>, |x_i|^2 + |g_j|^2), 0), NaN -> +inf: the bits of am_knn_search_f32(squared)
+ *     z_ij = fmaf(-d2, h_j, -c_j)        the same bits in both sweeps
+ *   A centre with a non-finite element, or with a theta_j for which h_j is no normal float32 number, sits at distance +inf
+ *   from every row: it contributes exactly 0 everywhere.
+ *
+ *   LOGLIK.  Rows are the evaluated points X, columns the centres.
+ *     out_loglik[i] = logsumexp_j z_ij - log M - (D / 2) log 2 pi      DEVICE double[N]; the online log-sum-exp of
+ *                     am_softmin_f32 (a running f32 maximum, the f64 sum of exp(z - max), exp in f64; the constants are added
+ *                     once, in f64, at the end); -inf for a row with a non-finite element (every distance +inf)
+ *     stats         = { sum of the finite out_loglik, rows with a finite one, rows without }   DEVICE double[3], overwritten
+ *   Lane and chunk partials are joined in a fixed order and the sum over the rows is a fixed tree over blocks of 256 rows
+ *   added in block order.
+ *
+ *   GRAD.  The swapped sweep - rows are the centres, columns the evaluated rows X - and one Adam step on theta.
+ *     loglik        DEVICE double[N]: out_loglik of a LOGLIK call with the same G, theta and X (the column's log-sum-exp is
+ *                   loglik + log M + (D / 2) log 2 pi, kept as two f32 halves); a column whose value is not finite and a
+ *                   padded column add exactly 0 to both sums
+ *     r_ij = exp(z_ij - lse_i) in f64,   A_j = sum_i r_ij,   B_j = sum_i r_ij d2_ij      f64, in a fixed order
+ *     n_finite      DEVICE double[1]: stats[1] of that LOGLIK call (0: the gradient is 0)
+ *     grad_j        = -(h_j B_j - (D / 2) A_j) / n_finite, h_j = 0.5 exp(-theta_j) in f64
+ *     Adam, beta = (0.9, 0.999), eps = 1e-8, bias-corrected with 1 - beta^step (step >= 1, HOST):
+ *       m <- 0.9 m + 0.1 grad;  v <- 0.999 v + 0.001 grad^2;  theta_out = clamp(theta - lr (m / bc1) / (sqrt(v / bc2) + eps),
+ *       theta_min, 30), every operation rounded once, in this order.  adam_m, adam_v: DEVICE double[M], updated in place;
+ *       theta_out: DEVICE double[M], may be theta.  theta_min (HOST) must be finite, at most 30, with 0.5 exp(-theta_min) a
+ *       normal float32 number.
+ *     out_a, out_b  OPTIONAL (may be NULL) DEVICE double[M]: A and B
+ *   No floating-point atomics: two calls at the same shapes return the same bits.  X, G as for am_knn_search_f32 (16-byte
+ *   aligned, ld % 4 == 0, ld >= D).  Workspace: the norms, three floats per column, and [column chunks][rows] partials
+ *   ((float, double) in LOGLIK, two doubles in GRAD).  Everything is validated before the first HIP call; the calls are
+ *   asynchronous and read nothing back.
+ * ------------------------------------------------------------------------- */
+size_t am_fld_loglik_workspace_bytes(int64_t N, int64_t M, int D);
+int am_fld_loglik_f32(const float* X, int64_t N, int64_t ldx, const float* G, int64_t M, int64_t ldg, int D,
+                      const double* theta, double* out_loglik, double* stats,
+                      void* ws, size_t ws_bytes, am_stream_t stream);
+size_t am_fld_grad_workspace_bytes(int64_t M, int64_t N, int D);
+int am_fld_grad_f32(const float* G, int64_t M, int64_t ldg, const float* X, int64_t N, int64_t ldx, int D,
+                    const double* theta, const double* loglik, const double* n_finite, double* adam_m, double* adam_v,
+                    int64_t step, double lr, double theta_min, double* theta_out, double* out_a, double* out_b,
+                    void* ws, size_t ws_bytes, am_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * PER-SAMPLE realism, ball count and rarity on the PRDC manifold (csrc/sample_scores.hip)   no counterpart in the reference
  *   X: the samples (N rows), Y: the manifold set (M rows), r_y: device float[M], the k-NN radius of row j of Y (what
  *   am_knn_radii_f32(Y, Y) returns).  One Gram pass on the exact f32 tile engine, no N x M matrix.  Per pair, all in f32:
