@@ -29,7 +29,7 @@
 // in the loglik sweep (mx, s for two rows) and 8 in the gradient sweep (A, B for two rows; |g|^2, h, -c of the rows wait in
 // LDS), whose epilogue has no maximum pass and loads its aux values four columns at a time.  __launch_bounds__(256, 2), two
 // workgroups per CU.
-#include "pairwise_common.h"
+#include "row_sweep.h"
 #include <float.h>
 #include <math.h>
 
@@ -42,51 +42,20 @@ constexpr int MERGE_THREADS = 256;
 constexpr double THETA_MAX = 30.0;
 constexpr double ADAM_B1 = 0.9, ADAM_B2 = 0.999, ADAM_EPS = 1e-8;
 
-// (mx, s) <- (mx, s) + (mx2, s2), as in softmin.hip (which stays as it is: its copy is not shared)
-__device__ __forceinline__ void lse_join(float& mx, double& s, float mx2, double s2) {
-    const float m = fmaxf(mx, mx2);
-    const double a = mx == m ? s : s * exp((double)mx - (double)m);
-    const double b = mx2 == m ? s2 : s2 * exp((double)mx2 - (double)m);
-    mx = m;
-    s = a + b;
-}
-
 __device__ __forceinline__ float z_of(float a, float norms, float h, float negc, float& d2) {
     d2 = clamp0(fmaf(-2.f, a, norms));
     return fmaf(-d2, h, negc);                       // d2 = +inf -> -inf (h is a positive normal number, -c is finite)
 }
 
-struct LoglikEpilogue {
-    const float* gnorm;
-    const float* hcol;                   // h_j
-    const float* ccol;                   // -c_j
-    int64_t nc;
-    float* aux;                          // LDS [2][3][128] : |g_j|^2 of the tile (+inf past nc), h_j (1 past nc), -c_j (0 past nc)
+struct LoglikEpilogue : ColumnAux<PAD_INF, PAD_ONE, PAD_ZERO> {      // |g_j|^2 of the tile, h_j, -c_j
     float xn[2];
     float mx[2];
     double s[2];
-    float aux_n, aux_h, aux_c;
-    const LaneInfo& L;
 
-    __device__ __forceinline__ LoglikEpilogue(const LaneInfo& l) : L(l) {}
-    __device__ __forceinline__ void aux_issue(int, int64_t qtile) {
-        if (L.tid < TB) {
-            const int64_t j = qtile * TB + L.tid;
-            aux_n = j < nc ? gnorm[j] : INFINITY;
-            aux_h = j < nc ? hcol[j] : 1.f;
-            aux_c = j < nc ? ccol[j] : 0.f;
-        }
-    }
-    __device__ __forceinline__ void aux_commit(int t) {
-        if (L.tid < TB) {
-            aux[(t & 1) * 3 * TB + L.tid] = aux_n;
-            aux[(t & 1) * 3 * TB + TB + L.tid] = aux_h;
-            aux[(t & 1) * 3 * TB + 2 * TB + L.tid] = aux_c;
-        }
-    }
+    __device__ __forceinline__ LoglikEpilogue(const LaneInfo& l) : ColumnAux<PAD_INF, PAD_ONE, PAD_ZERO>(l) {}
 
     __device__ __forceinline__ void finish(int t, int64_t, f32x16 (&acc)[2][2]) {
-        const float* a = aux + (t & 1) * 3 * TB + L.wm * 64 + L.h * 4;
+        const float* a = tile(t);
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt) {
             f32x4 gn[4], hq[4], cq[4];
@@ -102,12 +71,7 @@ struct LoglikEpilogue {
 #pragma unroll
                 for (int reg = 0; reg < 16; ++reg)
                     tmax = fmaxf(tmax, z_of(acc[mt][nt][reg], xn[nt] + gn[reg >> 2][reg & 3], hq[reg >> 2][reg & 3], cq[reg >> 2][reg & 3], d2));
-                const float mnew = fmaxf(mx[nt], tmax);
-                if (__any(mnew != mx[nt])) {                           // the maximum rose in some lane: rescale its sum
-                    if (mnew != mx[nt]) s[nt] *= exp((double)mx[nt] - (double)mnew);      // from -inf: 0 * exp(-inf) = 0
-                    mx[nt] = mnew;
-                }
-                const double ref = mnew == -INFINITY ? 0.0 : (double)mnew;                // nothing finite yet: every term is 0
+                const double ref = lse_raise(mx[nt], s[nt], tmax);
                 double sum = s[nt];
 #pragma unroll
                 for (int reg = 0; reg < 16; ++reg) {
@@ -121,40 +85,19 @@ struct LoglikEpilogue {
     }
 };
 
-struct GradEpilogue {
-    const float* xnorm;                  // |x_i|^2, +inf for a column without a finite l_i (fld_lse_columns_kernel)
-    const float* lhi;                    // lse_i = lhi + llo
-    const float* llo;
-    int64_t nc;
-    float* aux;                          // LDS [2][3][128] : |x_i|^2 of the tile (+inf past nc), the two halves of lse_i (0 past nc)
+// columns: |x_i|^2 (+inf for a row without a finite l_i: fld_lse_columns_kernel), then the two halves of lse_i = lhi + llo
+struct GradEpilogue : ColumnAux<PAD_INF, PAD_ZERO, PAD_ZERO> {
     const float* rowaux;                 // LDS [3][128] : |g_j|^2, h_j, -c_j of the workgroup's rows (not kept in registers)
     double A[2], B[2];
-    float aux_n, aux_h, aux_l;
-    const LaneInfo& L;
 
-    __device__ __forceinline__ GradEpilogue(const LaneInfo& l) : L(l) {}
-    __device__ __forceinline__ void aux_issue(int, int64_t qtile) {
-        if (L.tid < TB) {
-            const int64_t i = qtile * TB + L.tid;
-            aux_n = i < nc ? xnorm[i] : INFINITY;
-            aux_h = i < nc ? lhi[i] : 0.f;
-            aux_l = i < nc ? llo[i] : 0.f;
-        }
-    }
-    __device__ __forceinline__ void aux_commit(int t) {
-        if (L.tid < TB) {
-            aux[(t & 1) * 3 * TB + L.tid] = aux_n;
-            aux[(t & 1) * 3 * TB + TB + L.tid] = aux_h;
-            aux[(t & 1) * 3 * TB + 2 * TB + L.tid] = aux_l;
-        }
-    }
+    __device__ __forceinline__ GradEpilogue(const LaneInfo& l) : ColumnAux<PAD_INF, PAD_ZERO, PAD_ZERO>(l) {}
 
     __device__ __forceinline__ void finish(int t, int64_t, f32x16 (&acc)[2][2]) {
-        const float* a = aux + (t & 1) * 3 * TB + L.wm * 64 + L.h * 4;
+        const float* a = tile(t);
         float gn[2], h[2], negc[2];
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt) {
-            const int row = L.wn * 64 + nt * 32 + L.r;
+            const int row = sweep_row(0, L, nt);
             gn[nt] = rowaux[row];
             h[nt] = rowaux[TB + row];
             negc[nt] = rowaux[2 * TB + row];
@@ -233,15 +176,14 @@ fld_loglik_kernel(const float* __restrict__ X, int64_t N, int64_t ldx, const flo
     const int chunk = blockIdx.x % nchunks;            // the chunk work_item gave this workgroup: its slice of the partials
 
     LoglikEpilogue epi(L);
-    epi.gnorm = gnorm;
-    epi.hcol = hcol;
-    epi.ccol = ccol;
+    epi.src[0] = gnorm;
+    epi.src[1] = hcol;
+    epi.src[2] = ccol;
     epi.nc = M;
-    epi.aux = lds + ENGINE_LDS_FLOATS;
+    epi.lds = lds + ENGINE_LDS_FLOATS;
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) {
-        const int64_t i = w.prow0 + L.wn * 64 + nt * 32 + L.r;
-        epi.xn[nt] = i < N ? xnorm[i] : 0.f;
+        epi.xn[nt] = row_norm(xnorm, w.prow0, N, L, nt);
         epi.mx[nt] = -INFINITY;
         epi.s[nt] = 0.0;
     }
@@ -253,14 +195,13 @@ fld_loglik_kernel(const float* __restrict__ X, int64_t N, int64_t ldx, const flo
     float* mm = lds + 2 * TB * 4;
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) {
-        const int slot = (nt * 64 + L.wn * 32 + L.r) * 4 + (L.wm * 2 + L.h);
+        const int slot = join_slot(L, nt);
         ms[slot] = epi.s[nt];
         mm[slot] = epi.mx[nt];
     }
     __syncthreads();
     if (L.tid < 128) {
-        const int nt = L.tid >> 6, q = L.tid & 63;
-        const int64_t i = w.prow0 + (q >> 5) * 64 + nt * 32 + (q & 31);
+        const int64_t i = joined_row(w.prow0, L.tid);
         if (i < N) {
             float m = mm[L.tid * 4];
             double s = ms[L.tid * 4];
@@ -285,11 +226,11 @@ fld_grad_kernel(const float* __restrict__ G, int64_t M, int64_t ldg, const float
     const int chunk = blockIdx.x % nchunks;
 
     GradEpilogue epi(L);
-    epi.xnorm = xnorm;
-    epi.lhi = lhi;
-    epi.llo = llo;
+    epi.src[0] = xnorm;
+    epi.src[1] = lhi;
+    epi.src[2] = llo;
     epi.nc = N;
-    epi.aux = lds + ENGINE_LDS_FLOATS;
+    epi.lds = lds + ENGINE_LDS_FLOATS;
     float* rowaux = lds + ENGINE_LDS_FLOATS + 2 * 3 * TB;
     epi.rowaux = rowaux;
     if (L.tid < TB) {                                  // visible to finish() behind the pipeline's first barrier
@@ -310,14 +251,13 @@ fld_grad_kernel(const float* __restrict__ G, int64_t M, int64_t ldg, const float
     double* sb = sa + TB * 4;
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) {
-        const int slot = (nt * 64 + L.wn * 32 + L.r) * 4 + (L.wm * 2 + L.h);
+        const int slot = join_slot(L, nt);
         sa[slot] = epi.A[nt];
         sb[slot] = epi.B[nt];
     }
     __syncthreads();
     if (L.tid < 128) {
-        const int nt = L.tid >> 6, q = L.tid & 63;
-        const int64_t j = w.prow0 + (q >> 5) * 64 + nt * 32 + (q & 31);
+        const int64_t j = joined_row(w.prow0, L.tid);
         if (j < M) {
             double a = sa[L.tid * 4], b = sb[L.tid * 4];
 #pragma unroll
@@ -329,20 +269,6 @@ fld_grad_kernel(const float* __restrict__ G, int64_t M, int64_t ldg, const float
             part_b[(int64_t)chunk * M + j] = b;
         }
     }
-}
-
-// sum of the workgroup's values in a fixed tree
-__device__ __forceinline__ double block_sum_256(double v, double* s) {
-    s[threadIdx.x] = v;
-    __syncthreads();
-#pragma unroll
-    for (int w = MERGE_THREADS / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) s[threadIdx.x] += s[threadIdx.x + w];
-        __syncthreads();
-    }
-    const double r = s[0];
-    __syncthreads();
-    return r;
 }
 
 // the chunks' pairs of a row in chunk order -> l_i, and this block's { sum of the finite l_i, their number }
@@ -363,8 +289,10 @@ fld_loglik_merge_kernel(const float* __restrict__ part_mx, const double* __restr
             one = 1.0;
         }
     }
-    const double sum = block_sum_256(l, red);
-    const double cnt = block_sum_256(one, red);
+    const double sum = block_reduce_256<SumOp>(l, red);
+    __syncthreads();
+    const double cnt = block_reduce_256<SumOp>(one, red);
+    __syncthreads();                                   // guards nothing: kept so the kernel stays the program it was
     if (threadIdx.x == 0) {
         block_sums[2 * (int64_t)blockIdx.x] = sum;
         block_sums[2 * (int64_t)blockIdx.x + 1] = cnt;
@@ -380,8 +308,10 @@ fld_stats_kernel(const double* __restrict__ block_sums, int64_t nblocks, int64_t
         l += block_sums[2 * b];
         cnt += block_sums[2 * b + 1];
     }
-    const double sum = block_sum_256(l, red);
-    const double n = block_sum_256(cnt, red);
+    const double sum = block_reduce_256<SumOp>(l, red);
+    __syncthreads();
+    const double n = block_reduce_256<SumOp>(cnt, red);
+    __syncthreads();                                   // (as above)
     if (threadIdx.x == 0) {
         stats[0] = sum;
         stats[1] = n;
@@ -420,10 +350,7 @@ fld_grad_merge_kernel(const double* __restrict__ part_a, const double* __restric
     theta_out[j] = tn;
 }
 
-static bool shape_ok(int64_t rows, int64_t cols, int D) {
-    // one grid dimension holds row blocks x chunks
-    return rows >= 1 && cols >= 1 && D >= 1 && ceil_div(rows, TB) * 64 < (int64_t)0x7fffffff && ceil_div(cols, TB) < (int64_t)0x7fffffff;
-}
+static bool shape_ok(int64_t rows, int64_t cols, int D) { return sweep_shape_ok(rows, cols, D, COLUMNS_TILED); }
 
 struct LoglikBuffers {
     float *xn, *gn, *h, *negc, *part_mx;
@@ -498,16 +425,8 @@ extern "C" int am_fld_loglik_f32(const float* X, int64_t N, int64_t ldx, const f
     hipLaunchKernelGGL(fld::fld_columns_kernel, dim3((unsigned)ceil_div(M, fld::MERGE_THREADS)), dim3(fld::MERGE_THREADS), 0, st, theta,
                        M, 0.5 * (double)D, b.h, b.negc, b.gn);
     AM_LAUNCH_CHECK();
-    auto launch = [&](auto kernel) -> int {
-        AM_HIP_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), (int)fld::LDS_BYTES));
-        hipLaunchKernelGGL(kernel, dim3((unsigned)(ceil_div(N, TB) * nchunks)), dim3(ENGINE_THREADS), fld::LDS_BYTES, st, X, N, ldx,
-                           (const float*)b.xn, G, M, ldg, (const float*)b.gn, (const float*)b.h, (const float*)b.negc, D, nchunks,
-                           b.part_mx, b.part_s);
-        AM_LAUNCH_CHECK();
-        return AM_OK;
-    };
-    // the inner-dimension tail (D % 32 != 0) is a separate instantiation so the common kernel carries no tail code
-    rc = (D % BK) != 0 ? launch(&fld::fld_loglik_kernel<true>) : launch(&fld::fld_loglik_kernel<false>);
+    rc = launch_sweep(&fld::fld_loglik_kernel<false>, &fld::fld_loglik_kernel<true>, fld::LDS_BYTES, N, nchunks, D, st, X, N, ldx, b.xn, G,
+                      M, ldg, b.gn, b.h, b.negc, D, nchunks, b.part_mx, b.part_s);
     if (rc != AM_OK) return rc;
     const int64_t nblocks = ceil_div(N, fld::MERGE_THREADS);
     hipLaunchKernelGGL(fld::fld_loglik_merge_kernel, dim3((unsigned)nblocks), dim3(fld::MERGE_THREADS), 0, st, (const float*)b.part_mx,
@@ -548,15 +467,8 @@ extern "C" int am_fld_grad_f32(const float* G, int64_t M, int64_t ldg, const flo
     hipLaunchKernelGGL(fld::fld_lse_columns_kernel, dim3((unsigned)ceil_div(N, fld::MERGE_THREADS)), dim3(fld::MERGE_THREADS), 0, st,
                        loglik, N, fld::mixture_constant(M, D), b.xn, b.lhi, b.llo);
     AM_LAUNCH_CHECK();
-    auto launch = [&](auto kernel) -> int {
-        AM_HIP_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), (int)fld::GRAD_LDS_BYTES));
-        hipLaunchKernelGGL(kernel, dim3((unsigned)(ceil_div(M, TB) * nchunks)), dim3(ENGINE_THREADS), fld::GRAD_LDS_BYTES, st, G, M, ldg,
-                           (const float*)b.gn, (const float*)b.h, (const float*)b.negc, X, N, ldx, (const float*)b.xn,
-                           (const float*)b.lhi, (const float*)b.llo, D, nchunks, b.part_a, b.part_b);
-        AM_LAUNCH_CHECK();
-        return AM_OK;
-    };
-    rc = (D % BK) != 0 ? launch(&fld::fld_grad_kernel<true>) : launch(&fld::fld_grad_kernel<false>);
+    rc = launch_sweep(&fld::fld_grad_kernel<false>, &fld::fld_grad_kernel<true>, fld::GRAD_LDS_BYTES, M, nchunks, D, st, G, M, ldg, b.gn,
+                      b.h, b.negc, X, N, ldx, b.xn, b.lhi, b.llo, D, nchunks, b.part_a, b.part_b);
     if (rc != AM_OK) return rc;
     // the bias corrections 1 - beta^step on the host: the pow of the host formula
     const double bc1 = 1.0 - pow(fld::ADAM_B1, (double)step), bc2 = 1.0 - pow(fld::ADAM_B2, (double)step);

@@ -26,7 +26,7 @@
 // cluster that crosses segment borders leaves one partial sum per segment it touches - a segment has at most one cluster
 // that began before it (slot 0) and one that goes on behind it (slot 1) - and kmeans_update_finish_kernel adds them in
 // segment order.  Skewed cluster sizes cost nothing: the work is cut by rows, not by clusters.
-#include "pairwise_common.h"
+#include "row_sweep.h"
 
 namespace am {
 namespace kmeans {
@@ -39,29 +39,15 @@ constexpr int SEG_ROWS = 64;                                             // posi
 constexpr int UPD_THREADS = 64;
 constexpr int UPD_COLS = UPD_THREADS * 4;                                // columns per update workgroup
 
-struct AssignEpilogue {
-    const float* cnorm;
-    int64_t nc;
-    float* aux;                          // LDS [2][128] : |c_j|^2 of the tile (+inf past nc)
+struct AssignEpilogue : ColumnAux<PAD_INF> {            // |c_j|^2 of the tile (+inf past the end)
     float xn[2];
     unsigned long long best[2];
-    float aux_reg;
-    const LaneInfo& L;
 
-    __device__ __forceinline__ AssignEpilogue(const LaneInfo& l) : L(l) {}
-    __device__ __forceinline__ void aux_issue(int, int64_t qtile) {
-        if (L.tid < TB) {
-            const int64_t j = qtile * TB + L.tid;
-            aux_reg = j < nc ? cnorm[j] : INFINITY;
-        }
-    }
-    __device__ __forceinline__ void aux_commit(int t) {
-        if (L.tid < TB) aux[(t & 1) * TB + L.tid] = aux_reg;
-    }
+    __device__ __forceinline__ AssignEpilogue(const LaneInfo& l) : ColumnAux<PAD_INF>(l) {}
     __device__ __forceinline__ float last(int nt) const { return __uint_as_float((unsigned)(best[nt] >> 32)); }
 
     __device__ __forceinline__ void finish(int t, int64_t qtile, f32x16 (&acc)[2][2]) {
-        const float* a = aux + (t & 1) * TB + L.wm * 64 + L.h * 4;
+        const float* a = tile(t);
         const unsigned cbase = (unsigned)(qtile * TB + L.wm * 64 + L.h * 4);      // the lane's first column of the tile
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt) {
@@ -106,13 +92,12 @@ kmeans_assign_kernel(const float* __restrict__ X, int64_t N, int64_t ldx, const 
     const int chunk = blockIdx.x % nchunks;            // the chunk work_item gave this workgroup: its slice of `partial`
 
     AssignEpilogue epi(L);
-    epi.cnorm = cnorm;
+    epi.src[0] = cnorm;
     epi.nc = K;
-    epi.aux = lds + ENGINE_LDS_FLOATS;
+    epi.lds = lds + ENGINE_LDS_FLOATS;
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) {
-        const int64_t i = w.prow0 + L.wn * 64 + nt * 32 + L.r;
-        epi.xn[nt] = i < N ? xnorm[i] : 0.f;
+        epi.xn[nt] = row_norm(xnorm, w.prow0, N, L, nt);
         epi.best[nt] = EMPTY_KEY;
     }
     dense_pipeline_early<EV_DEFAULT, KTAIL>(C, K, ldc, LinearTiles{w.qtile0}, X, N, ldx, w.prow0, w.ntiles, D, lds, L, epi);
@@ -120,11 +105,10 @@ kmeans_assign_kernel(const float* __restrict__ X, int64_t N, int64_t ldx, const 
     // a row is covered by 4 keys (2 half-waves x 2 column-half waves): [2][64][4] keys through the staging slabs, free now
     unsigned long long* mg = reinterpret_cast<unsigned long long*>(lds);
 #pragma unroll
-    for (int nt = 0; nt < 2; ++nt) mg[(nt * 64 + L.wn * 32 + L.r) * 4 + (L.wm * 2 + L.h)] = epi.best[nt];
+    for (int nt = 0; nt < 2; ++nt) mg[join_slot(L, nt)] = epi.best[nt];
     __syncthreads();
     if (L.tid < 128) {
-        const int nt = L.tid >> 6, q = L.tid & 63;
-        const int64_t i = w.prow0 + (q >> 5) * 64 + nt * 32 + (q & 31);
+        const int64_t i = joined_row(w.prow0, L.tid);
         if (i < N) {
             const unsigned long long* src = mg + L.tid * 4;
             unsigned long long m = src[0];
@@ -133,18 +117,6 @@ kmeans_assign_kernel(const float* __restrict__ X, int64_t N, int64_t ldx, const 
             partial[(int64_t)chunk * N + i] = m;
         }
     }
-}
-
-// fixed-shape tree over the workgroup's values: the same order of additions on every call
-__device__ __forceinline__ double block_sum_256(double v, double* s) {
-    s[threadIdx.x] = v;
-    __syncthreads();
-#pragma unroll
-    for (int w = MERGE_THREADS / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) s[threadIdx.x] += s[threadIdx.x + w];
-        __syncthreads();
-    }
-    return s[0];
 }
 
 // smallest key of a row over all chunks -> (label, d2); no finite distance -> (-1, +inf), left out of the sum
@@ -167,7 +139,7 @@ kmeans_assign_merge_kernel(const unsigned long long* __restrict__ partial, int64
         d2_out[i] = d2;
         v = found ? (double)d2 : 0.0;
     }
-    const double total = block_sum_256(v, s);
+    const double total = block_reduce_256<SumOp>(v, s);
     if (threadIdx.x == 0) block_sums[blockIdx.x] = total;
 }
 
@@ -176,7 +148,7 @@ kmeans_inertia_kernel(const double* __restrict__ block_sums, int64_t nblocks, do
     __shared__ double s[MERGE_THREADS];
     double v = 0.0;
     for (int64_t j = threadIdx.x; j < nblocks; j += MERGE_THREADS) v += block_sums[j];
-    const double total = block_sum_256(v, s);
+    const double total = block_reduce_256<SumOp>(v, s);
     if (threadIdx.x == 0) inertia[0] = total;
 }
 
@@ -281,10 +253,7 @@ kmeans_update_finish_kernel(const int64_t* __restrict__ offsets, int64_t K, int 
     Cnew[c * ldcn + col] = __float_as_uint((float)(s / (double)cnt));
 }
 
-static bool assign_shape_ok(int64_t N, int64_t K, int D) {
-    // columns are the low 32 bits of a key (0xffffffff = none); one grid dimension holds row blocks x chunks
-    return N >= 1 && K >= 1 && D >= 1 && K < (int64_t)0xffffffffll && ceil_div(N, TB) * 64 < (int64_t)0x7fffffff;
-}
+static bool assign_shape_ok(int64_t N, int64_t K, int D) { return sweep_shape_ok(N, K, D, COLUMNS_KEYED); }
 
 struct AssignBuffers {
     float *xn, *cn;
@@ -335,15 +304,8 @@ extern "C" int am_kmeans_assign_f32(const float* X, int64_t N, int64_t ldx, cons
     hipStream_t st = static_cast<hipStream_t>(stream);
     if ((rc = launch_norms(X, N, ldx, D, b.xn, st)) != AM_OK) return rc;
     if ((rc = launch_norms(C, K, ldc, D, b.cn, st)) != AM_OK) return rc;
-    auto launch = [&](auto kernel) -> int {
-        AM_HIP_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), (int)kmeans::LDS_BYTES));
-        hipLaunchKernelGGL(kernel, dim3((unsigned)(ceil_div(N, TB) * nchunks)), dim3(ENGINE_THREADS), kmeans::LDS_BYTES, st, X, N, ldx,
-                           (const float*)b.xn, C, K, ldc, (const float*)b.cn, D, nchunks, b.partial);
-        AM_LAUNCH_CHECK();
-        return AM_OK;
-    };
-    // the inner-dimension tail (D % 32 != 0) is a separate instantiation so the common kernel carries no tail code
-    rc = (D % BK) != 0 ? launch(&kmeans::kmeans_assign_kernel<true>) : launch(&kmeans::kmeans_assign_kernel<false>);
+    rc = launch_sweep(&kmeans::kmeans_assign_kernel<false>, &kmeans::kmeans_assign_kernel<true>, kmeans::LDS_BYTES, N, nchunks, D, st, X, N,
+                      ldx, b.xn, C, K, ldc, b.cn, D, nchunks, b.partial);
     if (rc != AM_OK) return rc;
     const int64_t nblocks = ceil_div(N, kmeans::MERGE_THREADS);
     hipLaunchKernelGGL(kmeans::kmeans_assign_merge_kernel, dim3((unsigned)nblocks), dim3(kmeans::MERGE_THREADS), 0, st,

@@ -34,7 +34,7 @@
 //     KCAP 16:  64 list registers, __launch_bounds__(256, 2), two workgroups per CU
 //     KCAP 32: 128 list registers, __launch_bounds__(256, 1): ONE workgroup per CU (the lists alone are half of the 256
 //              registers a wave has at two per SIMD)
-#include "pairwise_common.h"
+#include "row_sweep.h"
 
 namespace am {
 namespace search {
@@ -98,7 +98,7 @@ struct KnnIndexEpilogue {
         if (diag) {
 #pragma unroll
             for (int nt = 0; nt < 2; ++nt) {
-                const int64_t rel = self_lo + (L.wn * 64 + nt * 32 + L.r) - c0;
+                const int64_t rel = self_lo + sweep_row(0, L, nt) - c0;
                 srel[nt] = (rel >= 0 && rel < 64) ? (int)rel : -1;
             }
         }
@@ -163,13 +163,14 @@ knn_search_kernel(const float* __restrict__ X, int64_t N, int64_t ldx, const flo
     epi.self_lo = self_offset >= 0 ? w.prow0 + self_offset : -2 * TB;
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) {
-        const int64_t i = w.prow0 + L.wn * 64 + nt * 32 + L.r;
-        epi.xn[nt] = i < N ? xnorm[i] : 0.f;
+        epi.xn[nt] = row_norm(xnorm, w.prow0, N, L, nt);
 #pragma unroll
         for (int s = 0; s < KCAP; ++s) epi.best[nt][s] = EMPTY_KEY;
     }
     dense_pipeline_early<EV_DEFAULT, KTAIL>(Y, M, ldy, LinearTiles{w.qtile0}, X, N, ldx, w.prow0, w.ntiles, D, lds, L, epi);
 
+    // (its own slot and row arithmetic, one P tile per pass: through join_slot / joined_row of row_sweep.h the register
+    // numbers of all six instantiations moved, and the 16-key form has no register to spare)
     // A P row is covered by 4 lists (2 half-waves x 2 Q-half waves): merged through LDS, the rows of one 32-row P tile
     // per wave at a time ([64][4][KCAP] keys: 64 KiB at KCAP = 32, inside the 72 KiB of staging slabs, which are free now)
     unsigned long long* mg = reinterpret_cast<unsigned long long*>(lds);
@@ -221,10 +222,7 @@ __global__ void __launch_bounds__(256) knn_search_merge_kernel(const unsigned lo
     }
 }
 
-static bool shape_ok(int64_t N, int64_t M, int D, int k) {
-    // columns are the low 32 bits of a key (0xffffffff = none); one grid dimension holds row blocks x chunks
-    return N >= 1 && M >= 1 && D >= 1 && k >= 1 && k <= MAX_K && M < (int64_t)0xffffffffll && ceil_div(N, TB) * 64 < (int64_t)0x7fffffff;
-}
+static bool shape_ok(int64_t N, int64_t M, int D, int k) { return k >= 1 && k <= MAX_K && sweep_shape_ok(N, M, D, COLUMNS_KEYED); }
 
 struct Buffers {
     float *xn, *yn;
@@ -240,15 +238,8 @@ template <int KCAP>
 static int run(const float* X, int64_t N, int64_t ldx, const float* xn, const float* Y, int64_t M, int64_t ldy, const float* yn,
                int D, int k, int nchunks, int64_t self_offset, int squared, unsigned long long* partial, float* out_dist,
                int64_t* out_idx, hipStream_t st) {
-    auto launch = [&](auto kernel) -> int {
-        AM_HIP_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), (int)LDS_BYTES));
-        hipLaunchKernelGGL(kernel, dim3((unsigned)(ceil_div(N, TB) * nchunks)), dim3(ENGINE_THREADS), LDS_BYTES, st, X, N, ldx, xn,
-                           Y, M, ldy, yn, D, nchunks, self_offset, partial);
-        AM_LAUNCH_CHECK();
-        return AM_OK;
-    };
-    // the inner-dimension tail (D % 32 != 0) is a separate instantiation so the common kernel carries no tail code
-    const int rc = (D % BK) != 0 ? launch(&knn_search_kernel<KCAP, true>) : launch(&knn_search_kernel<KCAP, false>);
+    const int rc = launch_sweep(&knn_search_kernel<KCAP, false>, &knn_search_kernel<KCAP, true>, LDS_BYTES, N, nchunks, D, st, X, N, ldx,
+                                xn, Y, M, ldy, yn, D, nchunks, self_offset, partial);
     if (rc != AM_OK) return rc;
     hipLaunchKernelGGL(knn_search_merge_kernel<KCAP>, dim3((unsigned)ceil_div(N, 256)), dim3(256), 0, st, partial, N, nchunks, k,
                        squared, out_dist, out_idx);
@@ -291,10 +282,8 @@ extern "C" int am_knn_search_f32(const float* X, int64_t N, int64_t ldx, const f
     hipStream_t st = static_cast<hipStream_t>(stream);
     // a column past the end excludes nothing; the kernel adds row indices to the offset
     if (self_offset >= M) self_offset = -1;
-    const bool self = (Y == X && M == N && ldy == ldx);
-    if ((rc = launch_norms(X, N, ldx, D, b.xn, st)) != AM_OK) return rc;
-    if (!self && (rc = launch_norms(Y, M, ldy, D, b.yn, st)) != AM_OK) return rc;
-    const float* yn = self ? b.xn : b.yn;
+    const float* yn;
+    if ((rc = launch_norms_pair(X, N, ldx, Y, M, ldy, D, b.xn, b.yn, st, &yn)) != AM_OK) return rc;
     switch (search::kcap_for(k)) {
         case 8:  return search::run<8>(X, N, ldx, b.xn, Y, M, ldy, yn, D, k, nchunks, self_offset, squared, b.partial, out_dist, out_idx, st);
         case 16: return search::run<16>(X, N, ldx, b.xn, Y, M, ldy, yn, D, k, nchunks, self_offset, squared, b.partial, out_dist, out_idx, st);

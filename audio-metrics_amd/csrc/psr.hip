@@ -30,7 +30,7 @@
 //
 // Register budget: 64 accumulators, 64 staging registers, 32 fragment registers, 4 product registers and 2 counts;
 // __launch_bounds__(256, 2), two workgroups per CU, no scratch (tests/test_psr_resources_cpu.py).
-#include "pairwise_common.h"
+#include "row_sweep.h"
 #include <float.h>
 #include <math.h>
 
@@ -40,31 +40,17 @@ namespace psr {
 constexpr size_t LDS_BYTES = (ENGINE_LDS_FLOATS + 2 * TB) * sizeof(float);       // staging slabs + [2][128] column norms
 constexpr int MERGE_THREADS = 256;
 
-struct PsrEpilogue {
-    const float* ynorm;
-    int64_t nc;
-    float* aux;                          // LDS [2][128] : |y_j|^2 of the tile (+inf past nc)
+struct PsrEpilogue : ColumnAux<PAD_INF> {               // |y_j|^2 of the tile (+inf past the end)
     float thr;                           // T' : T, or -inf when T == 0
     float inv;                           // (float)(1 / R)
     float xn[2];
     double prod[2];
     int cnt[2];
-    float aux_n;
-    const LaneInfo& L;
 
-    __device__ __forceinline__ PsrEpilogue(const LaneInfo& l) : L(l) {}
-    __device__ __forceinline__ void aux_issue(int, int64_t qtile) {
-        if (L.tid < TB) {
-            const int64_t j = qtile * TB + L.tid;
-            aux_n = j < nc ? ynorm[j] : INFINITY;
-        }
-    }
-    __device__ __forceinline__ void aux_commit(int t) {
-        if (L.tid < TB) aux[(t & 1) * TB + L.tid] = aux_n;
-    }
+    __device__ __forceinline__ PsrEpilogue(const LaneInfo& l) : ColumnAux<PAD_INF>(l) {}
 
     __device__ __forceinline__ void finish(int t, int64_t, f32x16 (&acc)[2][2]) {
-        const float* a = aux + (t & 1) * TB + L.wm * 64 + L.h * 4;
+        const float* a = tile(t);
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt) {
             f32x4 yn[4];
@@ -107,15 +93,14 @@ psr_kernel(const float* __restrict__ X, int64_t N, int64_t ldx, const float* __r
     const int chunk = blockIdx.x % nchunks;            // the chunk work_item gave this workgroup: its slice of the partials
 
     PsrEpilogue epi(L);
-    epi.ynorm = ynorm;
+    epi.src[0] = ynorm;
     epi.nc = M;
-    epi.aux = lds + ENGINE_LDS_FLOATS;
+    epi.lds = lds + ENGINE_LDS_FLOATS;
     epi.thr = thr;
     epi.inv = inv;
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) {
-        const int64_t i = w.prow0 + L.wn * 64 + nt * 32 + L.r;
-        epi.xn[nt] = i < N ? xnorm[i] : 0.f;
+        epi.xn[nt] = row_norm(xnorm, w.prow0, N, L, nt);
         epi.prod[nt] = 1.0;
         epi.cnt[nt] = 0;
     }
@@ -127,14 +112,13 @@ psr_kernel(const float* __restrict__ X, int64_t N, int64_t ldx, const float* __r
     int* mgc = reinterpret_cast<int*>(mgp + TB * 4);
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) {
-        const int slot = (nt * 64 + L.wn * 32 + L.r) * 4 + (L.wm * 2 + L.h);
+        const int slot = join_slot(L, nt);
         mgp[slot] = epi.prod[nt];
         mgc[slot] = epi.cnt[nt];
     }
     __syncthreads();
     if (L.tid < TB) {
-        const int nt = L.tid >> 6, q = L.tid & 63;
-        const int64_t i = w.prow0 + (q >> 5) * 64 + nt * 32 + (q & 31);
+        const int64_t i = joined_row(w.prow0, L.tid);
         if (i < N) {
             double p = mgp[L.tid * 4];
             int c = mgc[L.tid * 4];
@@ -147,18 +131,6 @@ psr_kernel(const float* __restrict__ X, int64_t N, int64_t ldx, const float* __r
             pcnt[(int64_t)chunk * N + i] = c;
         }
     }
-}
-
-// fixed-shape tree over the workgroup's values: the same order of additions on every call
-__device__ __forceinline__ double block_sum_256(double v, double* s) {
-    s[threadIdx.x] = v;
-    __syncthreads();
-#pragma unroll
-    for (int w = MERGE_THREADS / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) s[threadIdx.x] += s[threadIdx.x + w];
-        __syncthreads();
-    }
-    return s[0];
 }
 
 // the chunks' partials of a row in chunk order -> psr and count; block_sums[2 * block + {0, 1}] = the block's sums of both
@@ -182,9 +154,9 @@ psr_merge_kernel(const double* __restrict__ pprod, const int* __restrict__ pcnt,
         out_count[i] = c;
     }
     if (block_sums == nullptr) return;                 // (uniform over the grid)
-    const double sv = block_sum_256(v, red);
+    const double sv = block_reduce_256<SumOp>(v, red);
     __syncthreads();
-    const double sc = block_sum_256(cv, red);          // integers below 2^53: exact
+    const double sc = block_reduce_256<SumOp>(cv, red);          // integers below 2^53: exact
     if (threadIdx.x == 0) {
         block_sums[2 * (int64_t)blockIdx.x] = sv;
         block_sums[2 * (int64_t)blockIdx.x + 1] = sc;
@@ -199,19 +171,16 @@ psr_sums_kernel(const double* __restrict__ block_sums, int64_t nblocks, double* 
         v += block_sums[2 * j];
         cv += block_sums[2 * j + 1];
     }
-    const double sv = block_sum_256(v, red);
+    const double sv = block_reduce_256<SumOp>(v, red);
     __syncthreads();
-    const double sc = block_sum_256(cv, red);
+    const double sc = block_reduce_256<SumOp>(cv, red);
     if (threadIdx.x == 0) {
         out_sums[0] = sv;
         out_sums[1] = sc;
     }
 }
 
-static bool shape_ok(int64_t N, int64_t M, int D) {
-    // the shape rules of am_sample_scores_f32; one grid dimension holds row blocks x chunks
-    return N >= 1 && M >= 1 && D >= 1 && M < (int64_t)0xffffffffll && ceil_div(N, TB) * 64 < (int64_t)0x7fffffff;
-}
+static bool shape_ok(int64_t N, int64_t M, int D) { return sweep_shape_ok(N, M, D, COLUMNS_KEYED); }   // as am_sample_scores_f32
 
 struct Buffers {
     float *xn, *yn;
@@ -264,19 +233,10 @@ extern "C" int am_psr_f32(const float* X, int64_t N, int64_t ldx, const float* Y
     // (a radius below 1 / FLT_MAX: only d2 == 0 is in range, and 0 * FLT_MAX is the factor 0 that 0 * inf would not be)
     const float inv = 1.0 / radius > (double)FLT_MAX ? FLT_MAX : (float)(1.0 / radius);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const bool same = X == Y && N == M && ldx == ldy;      // a set against itself: one set of norms
-    if ((rc = launch_norms(X, N, ldx, D, b.xn, st)) != AM_OK) return rc;
-    if (!same && (rc = launch_norms(Y, M, ldy, D, b.yn, st)) != AM_OK) return rc;
-    const float* yn = same ? b.xn : b.yn;
-    auto launch = [&](auto kernel) -> int {
-        AM_HIP_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), (int)psr::LDS_BYTES));
-        hipLaunchKernelGGL(kernel, dim3((unsigned)(ceil_div(N, TB) * nchunks)), dim3(ENGINE_THREADS), psr::LDS_BYTES, st, X, N, ldx,
-                           (const float*)b.xn, Y, M, ldy, yn, D, nchunks, thr, inv, b.pprod, b.pcnt);
-        AM_LAUNCH_CHECK();
-        return AM_OK;
-    };
-    // the inner-dimension tail (D % 32 != 0) is a separate instantiation so the common kernel carries no tail code
-    rc = (D % BK) != 0 ? launch(&psr::psr_kernel<true>) : launch(&psr::psr_kernel<false>);
+    const float* yn;
+    if ((rc = launch_norms_pair(X, N, ldx, Y, M, ldy, D, b.xn, b.yn, st, &yn)) != AM_OK) return rc;
+    rc = launch_sweep(&psr::psr_kernel<false>, &psr::psr_kernel<true>, psr::LDS_BYTES, N, nchunks, D, st, X, N, ldx, b.xn, Y, M, ldy, yn,
+                      D, nchunks, thr, inv, b.pprod, b.pcnt);
     if (rc != AM_OK) return rc;
     const int64_t nblocks = ceil_div(N, psr::MERGE_THREADS);
     hipLaunchKernelGGL(psr::psr_merge_kernel, dim3((unsigned)nblocks), dim3(psr::MERGE_THREADS), 0, st, (const double*)b.pprod,

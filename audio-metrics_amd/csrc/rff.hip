@@ -26,7 +26,7 @@
 // symmetric.  Chunks run in stream order, so the sum is in chunk order; no floating-point atomics anywhere (the only atomic is
 // the integer count of non-finite rows): two calls return the same bits.  The workspace is the feature buffer, the partials
 // and the row flags of ONE chunk: it does not grow with n past RFF_CHUNK_ROWS rows.
-#include "pairwise_common.h"
+#include "row_sweep.h"
 #include "f64_engine.h"
 #include <algorithm>
 #include <cmath>
@@ -35,6 +35,7 @@ namespace am {
 namespace rff {
 
 constexpr size_t FEATURE_LDS_BYTES = ENGINE_LDS_FLOATS * sizeof(float);
+static_assert(2 * FEATURE_LDS_BYTES <= 160 * 1024, "__launch_bounds__(ENGINE_THREADS, 2): two workgroups share the 160 KiB of a CU");
 constexpr int MAX_FEATURES = 1024;        // R: the 2048 x 2048 eigenproblem is what am_eigh_sym_f64 is used with
 constexpr int64_t CHUNK_ROWS = 4096;      // rows of X per chunk of the moment: [2R][4096] doubles = 64 MiB at R = 1024
 constexpr int FLAG_THREADS = 256;
@@ -225,15 +226,8 @@ static int launch_features(const float* X, int64_t nrows, int64_t ldx, int D, co
                        bad, count);
     AM_LAUNCH_CHECK();
     const int nchunks = choose_chunks(nrows, R);
-    auto launch = [&](auto kernel) -> int {
-        AM_HIP_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), (int)FEATURE_LDS_BYTES));
-        hipLaunchKernelGGL(kernel, dim3((unsigned)(ceil_div(nrows, TB) * nchunks)), dim3(ENGINE_THREADS), FEATURE_LDS_BYTES, st, X, nrows,
-                           ldx, W, R, ldw, D, nchunks, inv_bw, bw2_dev, (const int*)bad, F, ldo);
-        AM_LAUNCH_CHECK();
-        return AM_OK;
-    };
-    // the inner-dimension tail (D % 32 != 0) is a separate instantiation so the common kernel carries no tail code
-    return (D % BK) != 0 ? launch(&rff_features_kernel<true>) : launch(&rff_features_kernel<false>);
+    return launch_sweep(&rff_features_kernel<false>, &rff_features_kernel<true>, FEATURE_LDS_BYTES, nrows, nchunks, D, st, X, nrows, ldx, W,
+                        R, ldw, D, nchunks, inv_bw, bw2_dev, bad, F, ldo);
 }
 
 struct FeatureBuffers {

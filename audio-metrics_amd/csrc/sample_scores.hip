@@ -41,7 +41,7 @@
 //
 // Register budget: 64 accumulators, 64 staging registers, 32 fragment registers, 8 key registers and 2 counts;
 // __launch_bounds__(256, 2), two workgroups per CU (2 x 75 KiB of LDS), no scratch (tests/test_sample_scores_resources_cpu.py).
-#include "pairwise_common.h"
+#include "row_sweep.h"
 
 namespace am {
 namespace scores {
@@ -187,8 +187,7 @@ sample_scores_kernel(const float* __restrict__ X, int64_t N, int64_t ldx, const 
     epi.aux = lds + ENGINE_LDS_FLOATS;
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) {
-        const int64_t i = w.prow0 + L.wn * 64 + nt * 32 + L.r;
-        epi.xn[nt] = i < N ? xnorm[i] : 0.f;
+        epi.xn[nt] = row_norm(xnorm, w.prow0, N, L, nt);
         epi.kmax[nt] = 0ull;
         epi.kmin[nt] = NO_MEMBER;
         epi.cnt[nt] = 0;
@@ -202,15 +201,14 @@ sample_scores_kernel(const float* __restrict__ X, int64_t N, int64_t ldx, const 
     int* mgcnt = reinterpret_cast<int*>(mgmin + TB * 4);
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) {
-        const int slot = (nt * 64 + L.wn * 32 + L.r) * 4 + (L.wm * 2 + L.h);
+        const int slot = join_slot(L, nt);
         mgmax[slot] = epi.kmax[nt];
         mgmin[slot] = epi.kmin[nt];
         mgcnt[slot] = epi.cnt[nt];
     }
     __syncthreads();
     if (L.tid < TB) {
-        const int nt = L.tid >> 6, q = L.tid & 63;
-        const int64_t i = w.prow0 + (q >> 5) * 64 + nt * 32 + (q & 31);
+        const int64_t i = joined_row(w.prow0, L.tid);
         if (i < N) {
             unsigned long long hi = mgmax[L.tid * 4], lo = mgmin[L.tid * 4];
             int c = mgcnt[L.tid * 4];
@@ -253,10 +251,7 @@ sample_scores_merge_kernel(const unsigned long long* __restrict__ pmax, const un
     out_rarity_idx[i] = member ? (int64_t)(unsigned)lo : (int64_t)-1;
 }
 
-static bool shape_ok(int64_t N, int64_t M, int D) {
-    // columns are the low 32 bits of a key; one grid dimension holds row blocks x chunks
-    return N >= 1 && M >= 1 && D >= 1 && M < (int64_t)0xffffffffll && ceil_div(N, TB) * 64 < (int64_t)0x7fffffff;
-}
+static bool shape_ok(int64_t N, int64_t M, int D) { return sweep_shape_ok(N, M, D, COLUMNS_KEYED); }
 
 struct Buffers {
     float *xn, *yn, *thr, *rad;
@@ -310,22 +305,12 @@ extern "C" int am_sample_scores_f32(const float* X, int64_t N, int64_t ldx, cons
     AM_REQUIRE(c.ok(), AM_ERR_WORKSPACE, "workspace too small: need %zu bytes (am_sample_scores_workspace_bytes), have %zu", c.off,
                ws_bytes);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const bool self = (Y == X && M == N && ldy == ldx);
-    if ((rc = launch_norms(X, N, ldx, D, b.xn, st)) != AM_OK) return rc;
-    if (!self && (rc = launch_norms(Y, M, ldy, D, b.yn, st)) != AM_OK) return rc;
-    const float* yn = self ? b.xn : b.yn;
+    const float* yn;
+    if ((rc = launch_norms_pair(X, N, ldx, Y, M, ldy, D, b.xn, b.yn, st, &yn)) != AM_OK) return rc;
     hipLaunchKernelGGL(scores::scores_columns_kernel, dim3((unsigned)ceil_div(M, 256)), dim3(256), 0, st, r_y, M, b.rad, b.thr);
     AM_LAUNCH_CHECK();
-    auto launch = [&](auto kernel) -> int {
-        AM_HIP_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), (int)scores::LDS_BYTES));
-        hipLaunchKernelGGL(kernel, dim3((unsigned)(ceil_div(N, TB) * nchunks)), dim3(ENGINE_THREADS), scores::LDS_BYTES, st, X, N, ldx,
-                           (const float*)b.xn, Y, M, ldy, yn, (const float*)b.thr, (const float*)b.rad, D, nchunks, b.pmax, b.pmin,
-                           b.pcnt);
-        AM_LAUNCH_CHECK();
-        return AM_OK;
-    };
-    // the inner-dimension tail (D % 32 != 0) is a separate instantiation so the common kernel carries no tail code
-    rc = (D % BK) != 0 ? launch(&scores::sample_scores_kernel<true>) : launch(&scores::sample_scores_kernel<false>);
+    rc = launch_sweep(&scores::sample_scores_kernel<false>, &scores::sample_scores_kernel<true>, scores::LDS_BYTES, N, nchunks, D, st, X,
+                      N, ldx, b.xn, Y, M, ldy, yn, b.thr, b.rad, D, nchunks, b.pmax, b.pmin, b.pcnt);
     if (rc != AM_OK) return rc;
     hipLaunchKernelGGL(scores::sample_scores_merge_kernel, dim3((unsigned)ceil_div(N, scores::MERGE_THREADS)),
                        dim3(scores::MERGE_THREADS), 0, st, (const unsigned long long*)b.pmax, (const unsigned long long*)b.pmin,

@@ -24,7 +24,7 @@
 //
 // Register budget: the assign's (64 accumulators, 64 staging registers, 32 fragment registers) with 6 registers of state
 // per lane - mx and s for two rows - in place of its 4 key registers; __launch_bounds__(256, 2), two workgroups per CU.
-#include "pairwise_common.h"
+#include "row_sweep.h"
 #include <float.h>
 #include <math.h>
 
@@ -33,15 +33,6 @@ namespace softmin {
 
 constexpr size_t LDS_BYTES = (ENGINE_LDS_FLOATS + 2 * 2 * TB) * sizeof(float);   // staging slabs + [2][2][128]: |y_j|^2, g_j / eps
 constexpr int MERGE_THREADS = 256;
-
-// (mx, s) <- (mx, s) + (mx2, s2).  The side that holds the maximum keeps its sum as it is; an empty side (-inf, 0) adds 0.
-__device__ __forceinline__ void lse_join(float& mx, double& s, float mx2, double s2) {
-    const float m = fmaxf(mx, mx2);
-    const double a = mx == m ? s : s * exp((double)mx - (double)m);
-    const double b = mx2 == m ? s2 : s2 * exp((double)mx2 - (double)m);
-    mx = m;
-    s = a + b;
-}
 
 struct SoftminEpilogue {
     const float* ynorm;
@@ -89,12 +80,7 @@ struct SoftminEpilogue {
 #pragma unroll
                 for (int reg = 0; reg < 16; ++reg)
                     tmax = fmaxf(tmax, z_of(acc[mt][nt][reg], xn[nt] + yn[reg >> 2][reg & 3], gq[reg >> 2][reg & 3]));
-                const float mnew = fmaxf(mx[nt], tmax);
-                if (__any(mnew != mx[nt])) {                           // the maximum rose in some lane: rescale its sum
-                    if (mnew != mx[nt]) s[nt] *= exp((double)mx[nt] - (double)mnew);      // from -inf: 0 * exp(-inf) = 0
-                    mx[nt] = mnew;
-                }
-                const double ref = mnew == -INFINITY ? 0.0 : (double)mnew;                // nothing finite yet: every term is 0
+                const double ref = lse_raise(mx[nt], s[nt], tmax);
                 double sum = s[nt];
 #pragma unroll
                 for (int reg = 0; reg < 16; ++reg) {
@@ -134,8 +120,7 @@ softmin_kernel(const float* __restrict__ X, int64_t N, int64_t ldx, const float*
     epi.hie = hie;
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) {
-        const int64_t i = w.prow0 + L.wn * 64 + nt * 32 + L.r;
-        epi.xn[nt] = i < N ? xnorm[i] : 0.f;
+        epi.xn[nt] = row_norm(xnorm, w.prow0, N, L, nt);
         epi.mx[nt] = -INFINITY;
         epi.s[nt] = 0.0;
     }
@@ -147,14 +132,13 @@ softmin_kernel(const float* __restrict__ X, int64_t N, int64_t ldx, const float*
     float* mm = lds + 2 * TB * 4;
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) {
-        const int slot = (nt * 64 + L.wn * 32 + L.r) * 4 + (L.wm * 2 + L.h);
+        const int slot = join_slot(L, nt);
         ms[slot] = epi.s[nt];
         mm[slot] = epi.mx[nt];
     }
     __syncthreads();
     if (L.tid < 128) {
-        const int nt = L.tid >> 6, q = L.tid & 63;
-        const int64_t i = w.prow0 + (q >> 5) * 64 + nt * 32 + (q & 31);
+        const int64_t i = joined_row(w.prow0, L.tid);
         if (i < N) {
             float m = mm[L.tid * 4];
             double s = ms[L.tid * 4];
@@ -207,10 +191,7 @@ softmin_merge_kernel(const float* __restrict__ part_mx, const double* __restrict
     }
 }
 
-static bool shape_ok(int64_t N, int64_t M, int D) {
-    // one grid dimension holds row blocks x chunks
-    return N >= 1 && M >= 1 && D >= 1 && ceil_div(N, TB) * 64 < (int64_t)0x7fffffff && ceil_div(M, TB) < (int64_t)0x7fffffff;
-}
+static bool shape_ok(int64_t N, int64_t M, int D) { return sweep_shape_ok(N, M, D, COLUMNS_TILED); }
 
 struct Buffers {
     float *xn, *yn, *ge, *part_mx;
@@ -256,23 +237,13 @@ extern "C" int am_softmin_f32(const float* X, int64_t N, int64_t ldx, const floa
     softmin::carve(c, N, M, nchunks, b);
     AM_REQUIRE(c.ok(), AM_ERR_WORKSPACE, "workspace too small: need %zu bytes (am_softmin_workspace_bytes), have %zu", c.off, ws_bytes);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const bool same = X == Y && N == M && ldx == ldy;      // a set against itself: one set of norms
-    if ((rc = launch_norms(X, N, ldx, D, b.xn, st)) != AM_OK) return rc;
-    if (!same && (rc = launch_norms(Y, M, ldy, D, b.yn, st)) != AM_OK) return rc;
-    const float* yn = same ? b.xn : b.yn;
+    const float* yn;
+    if ((rc = launch_norms_pair(X, N, ldx, Y, M, ldy, D, b.xn, b.yn, st, &yn)) != AM_OK) return rc;
     hipLaunchKernelGGL(softmin::softmin_columns_kernel, dim3((unsigned)ceil_div(M, softmin::MERGE_THREADS)),
                        dim3(softmin::MERGE_THREADS), 0, st, g, M, eps, b.ge);
     AM_LAUNCH_CHECK();
-    const float hie = (float)(0.5 / eps);
-    auto launch = [&](auto kernel) -> int {
-        AM_HIP_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), (int)softmin::LDS_BYTES));
-        hipLaunchKernelGGL(kernel, dim3((unsigned)(ceil_div(N, TB) * nchunks)), dim3(ENGINE_THREADS), softmin::LDS_BYTES, st, X, N, ldx,
-                           (const float*)b.xn, Y, M, ldy, yn, (const float*)b.ge, D, nchunks, hie, b.part_mx, b.part_s);
-        AM_LAUNCH_CHECK();
-        return AM_OK;
-    };
-    // the inner-dimension tail (D % 32 != 0) is a separate instantiation so the common kernel carries no tail code
-    rc = (D % BK) != 0 ? launch(&softmin::softmin_kernel<true>) : launch(&softmin::softmin_kernel<false>);
+    rc = launch_sweep(&softmin::softmin_kernel<false>, &softmin::softmin_kernel<true>, softmin::LDS_BYTES, N, nchunks, D, st, X, N, ldx,
+                      b.xn, Y, M, ldy, yn, b.ge, D, nchunks, (float)(0.5 / eps), b.part_mx, b.part_s);
     if (rc != AM_OK) return rc;
     if (stats != nullptr) AM_HIP_TRY(hipMemsetAsync(stats, 0, 2 * sizeof(double), st));
     hipLaunchKernelGGL(softmin::softmin_merge_kernel, dim3((unsigned)ceil_div(N, softmin::MERGE_THREADS)), dim3(softmin::MERGE_THREADS),

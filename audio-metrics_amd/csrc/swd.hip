@@ -26,7 +26,7 @@
 // of the LARGER side: it overlaps atoms floor(i nb / na) .. ceil((i + 1) nb / na) - 1 of the smaller one (at most two) with
 // integer weights min((i + 1) nb, (j + 1) na) - max(i nb, j na), exact in int64 and in a double.  Terms, block sums and the
 // row sum are f64 in a fixed order, divided by na nb once.  No floating-point atomics: two calls return the same bits.
-#include "pairwise_common.h"
+#include "row_sweep.h"
 
 namespace am {
 namespace swd {
@@ -270,7 +270,7 @@ sliced_w_finish_kernel(const double* __restrict__ part, const int* __restrict__ 
 }
 
 static bool project_shape_ok(int64_t N, int64_t L, int D) {
-    return N >= 1 && L >= 1 && D >= 1 && ceil_div(N, TB) * 64 < (int64_t)0x7fffffff;     // one grid dimension: row blocks x chunks
+    return sweep_shape_ok(N, L, D, COLUMNS_ANY);
 }
 static int64_t sort_tmp_ld(int64_t N) { return ceil_div(N, 4) * 4; }
 static bool sort_shape_ok(int64_t L, int64_t N) {                                       // one workgroup per row; tmp of < 2^42 bytes
@@ -298,15 +298,8 @@ extern "C" int am_sliced_project_f32(const float* X, int64_t N, int64_t ldx, con
                (long long)L);
     const int nchunks = choose_chunks(N, L);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    auto launch = [&](auto kernel) -> int {
-        AM_HIP_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), (int)swd::PROJECT_LDS_BYTES));
-        hipLaunchKernelGGL(kernel, dim3((unsigned)(ceil_div(N, TB) * nchunks)), dim3(ENGINE_THREADS), swd::PROJECT_LDS_BYTES, st, X, N,
-                           ldx, Theta, L, ldt, D, nchunks, Z, ldz);
-        AM_LAUNCH_CHECK();
-        return AM_OK;
-    };
-    // the inner-dimension tail (D % 32 != 0) is a separate instantiation so the common kernel carries no tail code
-    return (D % BK) != 0 ? launch(&swd::sliced_project_kernel<true>) : launch(&swd::sliced_project_kernel<false>);
+    return launch_sweep(&swd::sliced_project_kernel<false>, &swd::sliced_project_kernel<true>, swd::PROJECT_LDS_BYTES, N, nchunks, D, st, X,
+                        N, ldx, Theta, L, ldt, D, nchunks, Z, ldz);
 }
 
 extern "C" size_t am_sort_rows_workspace_bytes(int64_t L, int64_t N) {

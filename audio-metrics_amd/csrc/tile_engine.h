@@ -3,7 +3,11 @@
 // Every dense contraction of the hot path that has two row-major operands with a
 // shared, contiguous inner (feature) dimension goes through this engine:
 //   * pairwise squared distances for the k-NN radii / PRDC counts (pairwise.hip),
-//   * the three Gram blocks per subset of the kernel distance (kd.hip).
+//   * the three Gram blocks per subset of the kernel distance (kd.hip) and the kernel sums of kad*.hip / mmd_*.hip,
+//   * the row sweeps - every row of one set against all rows of another, one epilogue per metric: the search
+//     (knn_search.hip), the k-means assign (kmeans.hip), the per-sample scores (sample_scores.hip), the soft-min
+//     (softmin.hip), the scoring rule (psr.hip), both sweeps of fld.hip, and the tile-storing projections of swd.hip
+//     and rff.hip.  What those share beyond the pipeline is in row_sweep.h.
 // A workgroup is 256 threads = 4 wave64 in a 2x2 arrangement; each wave owns a
 // 64x64 sub-tile = 2x2 MFMA tiles of 32x32 (64 accumulator VGPRs).
 //

@@ -4,8 +4,9 @@
     python tools/isa_compare.py parent.s change.s [name-substring]
 
 Each file is split at its kernel labels; comments, directives and blank lines are dropped, and what remains of each kernel
-(instructions and local labels) is compared text for text.  For a kernel that differs the differing lines and the counts of
-the instructions that make up a pipeline stage are printed.  Exit status 0: the same kernels, every one identical."""
+(instructions and local labels) is compared text for text; a local label .LBB<f>_<n> is read without <f>, the position of its
+function in the file, which moves when a function is added or removed above it.  For a kernel that differs the differing
+lines and the counts of the instructions that make up a pipeline stage are printed.  Exit status 0: the same kernels, every one identical."""
 import difflib
 import re
 import sys
@@ -37,7 +38,7 @@ def kernels(path, want):
             continue
         text = line.split(";")[0].strip()
         if text and not (text.startswith(".") and not text.endswith(":")):
-            body.append(re.sub(r"\s+", " ", text))
+            body.append(re.sub(r"\.LBB\d+_", ".LBB_", re.sub(r"\s+", " ", text)))
     return out
 
 
