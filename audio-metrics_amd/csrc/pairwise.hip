@@ -55,39 +55,6 @@ struct DenseRows {            // rows base + (tile0 + t) * 128 + local row, zero
     }
 };
 
-// XCD-grouped form of the same (row block, column chunk) grid for the f16 filter kernels, whose operand traffic is
-// 16x the exact kernels' per unit of time and therefore has to come from L2: block b runs on XCD b % 8
-// (MI355X_MICROARCH.md, workgroup dispatch), and the ~64 workgroups resident on one XCD should share few row blocks
-// and few column chunks.  The b / 8-th work item of an XCD is item (b / 8) % 64 of that XCD's (b / 8) / 64-th GROUP of
-// grp_rows row blocks x (64 / grp_rows) chunks: a group keeps grp_rows x 128 P rows (f16: 128 KB per block) resident
-// in the 4 MB L2 while its chunks stream past, and each Q tile is fetched once per group instead of once per
-// workgroup.  Grid: cross_grouped_blocks().  Items past the grid's edge come back with ntiles = 0.
-static inline int64_t cross_grouped_blocks(int64_t row_blocks, int nchunks, int grp_rows) {
-    const int grp_chunks = 64 / grp_rows;
-    const int64_t groups = ceil_div(row_blocks, grp_rows) * ceil_div(nchunks, grp_chunks);
-    return ceil_div(groups, 8) * 8 * 64;
-}
-__device__ __forceinline__ WorkItem work_item_grouped(int64_t q_tiles, int nchunks, int64_t row_blocks, int grp_rows) {
-    const int grp_chunks = 64 / grp_rows;
-    const int64_t cgroups = (nchunks + grp_chunks - 1) / grp_chunks;
-    const int xcd = blockIdx.x & 7;
-    const int64_t seq = blockIdx.x >> 3;
-    const int64_t g = (seq >> 6) * 8 + xcd;
-    const int within = (int)(seq & 63);
-    const int64_t rb = (g / cgroups) * grp_rows + within / grp_chunks;
-    const int chunk = (int)((g % cgroups) * grp_chunks + within % grp_chunks);
-    WorkItem w;
-    w.prow0 = rb * TB;
-    if (rb >= row_blocks || chunk >= nchunks) {
-        w.qtile0 = 0;
-        w.ntiles = 0;
-        return w;
-    }
-    w.qtile0 = q_tiles * chunk / nchunks;
-    w.ntiles = (int)(q_tiles * (chunk + 1) / nchunks - w.qtile0);
-    return w;
-}
-
 // the generic (gather) pipeline numbers tiles locally; shift them to absolute Q tile indices
 template <class Epi>
 struct OffsetEpilogue {
@@ -262,7 +229,6 @@ struct KnnSymEpilogue {
     uint2* wgq;                 // this workgroup's append region in global memory: (row, d2 bits)
     int* qn;                    // LDS slot counter of that region
     int qcap;
-    int ablate;                 // timing experiments only (AM_KNN_SYM_ABL): 1 = no mirrored test, 2 = no lane-local lists
     float xn[2];
     float flt[2];               // bound of this lane's own rows at workgroup start: larger values cannot matter
     bool rowok[2];
@@ -298,7 +264,7 @@ struct KnnSymEpilogue {
     }
     __device__ __forceinline__ void finish(int t, int64_t qtile, f32x16 (&acc)[2][2]) {
         const float* a = aux + (t & 1) * 2 * TB + L.wm * 64 + L.h * 4;
-        const bool mirror = (qtile != pblock) && !(ablate & 1);   // the diagonal tile already holds both directions
+        const bool mirror = qtile != pblock;               // the diagonal tile already holds both directions
         const int64_t jbase = qtile * TB + L.wm * 64 + L.h * 4;
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt) {
@@ -322,7 +288,7 @@ struct KnnSymEpilogue {
                 }
                 tmin = fmaxf(tmin, 0.f);
                 // <= : an entry EQUAL to the bound may be the (k+1)-th smallest itself
-                if (!(ablate & 2) && __any(tmin < best[nt][KCAP - 1] && tmin <= flt[nt])) {
+                if (__any(tmin < best[nt][KCAP - 1] && tmin <= flt[nt])) {
 #pragma unroll
                     for (int reg = 0; reg < 16; ++reg) {
                         const float d2 = clamp0(fmaf(-2.f, acc[mt][nt][reg], xn[nt] + yn[reg >> 2][reg & 3]));
@@ -348,8 +314,8 @@ template <int KCAP, bool KTAIL>
 __global__ void __launch_bounds__(ENGINE_THREADS, 2)
 knn_sym_kernel(const float* __restrict__ X, int64_t N, int64_t ld, const float* __restrict__ xnorm, float* thr, int D,
                int win_tiles, int nwin, int per_win, int k1, float* __restrict__ partial, float* __restrict__ cand,
-               int* __restrict__ cnt, int cap, uint2* __restrict__ wgq, int qcap, int* __restrict__ wgq_count, int ablate,
-               int part, int nparts) {
+               int* __restrict__ cnt, int cap, uint2* __restrict__ wgq, int qcap, int* __restrict__ wgq_count, int part,
+               int nparts) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const LaneInfo L;
     const int64_t T = (N + TB - 1) / TB;
@@ -374,7 +340,6 @@ knn_sym_kernel(const float* __restrict__ X, int64_t N, int64_t ld, const float* 
     epi.wgq = wgq + (int64_t)blockIdx.x * qcap;
     epi.qn = reinterpret_cast<int*>(lds + ENGINE_LDS_FLOATS + 4 * TB);
     epi.qcap = qcap;
-    epi.ablate = ablate;
     if (L.tid == 0) *epi.qn = 0;                    // visible after the pipeline's first barrier
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) {
@@ -895,8 +860,8 @@ static int launch_knn_sym(const float* X, int64_t N, int64_t ld, const float* xn
         AM_HIP_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), (int)PAIRWISE_LDS_BYTES + 16));
         clock_begin(AM_KERNEL_KNN, st);
         hipLaunchKernelGGL(kernel, dim3(nwg), dim3(ENGINE_THREADS), PAIRWISE_LDS_BYTES + 16, st,
-                           X, N, ld, xn, thr, D, win_tiles, nwin, per_win, k1, partial, cand, cnt, cap, wgq, qcap, wgq_count,
-                           env_int("AM_KNN_SYM_ABL", 0), part, nparts);
+                           X, N, ld, xn, thr, D, win_tiles, nwin, per_win, k1, partial, cand, cnt, cap, wgq, qcap, wgq_count, part,
+                           nparts);
         clock_end(AM_KERNEL_KNN, st);
         AM_LAUNCH_CHECK();
         return AM_OK;
@@ -935,7 +900,7 @@ struct KnnPlan {
 
 static KnnPlan plan_knn(int64_t N, int64_t M, int D, int k, bool self, bool partitioned = false) {
     static const int sym_min = env_int("AM_KNN_SYM_MIN_ROWS", 8192);
-    static const int sym_min_dim = env_int("AM_KNN_SYM_MIN_DIM", 128);
+    constexpr int sym_min_dim = 128;
     static const int cap_env = env_int("AM_KNN_SYM_CAP", 0);
     // Column sample of the bound pre-pass: every `stride`-th tile.  16 up to ~32 000 rows; larger sets keep about eight sampled
     // 256-row tiles (stride up to 48): the pre-pass costs N x N / stride pairs, and a bound from a third of the columns queues
@@ -953,7 +918,6 @@ static KnnPlan plan_knn(int64_t N, int64_t M, int D, int k, bool self, bool part
         const int64_t cap = D >= 384 ? 48 : D >= 192 ? 32 : D >= 96 ? 24 : 16;
         stride = (int)std::min<int64_t>(cap, std::max<int64_t>(16, ceil_div(N, 256) / 8));
     }
-    const int pre_windows = 0;
     KnnPlan p;
     p.tile_rows = TB;
     p.kcap = kcap_for(k + 1);
@@ -971,14 +935,13 @@ static KnnPlan plan_knn(int64_t N, int64_t M, int D, int k, bool self, bool part
     p.pre_chunks = 1;
     p.qcap = 0;
     p.nwg = 0;
-    p.pre_windows = pre_windows;
+    p.pre_windows = 0;
     if (!p.sym) {
         p.nchunks = choose_chunks(N, M);
         return p;
     }
     // the f16 filter sweep of k <= 10 runs on the 256 x 256 engine: row blocks and column tiles of 256 rows
-    static const int wide_on = env_int("AM_KNN_WIDE", 1);
-    const bool wide = wide_on != 0 && knn_fast_enabled(N, D) && p.kcap <= KNN_WIDE_MAX_KCAP && N >= 4 * 256;
+    const bool wide = knn_fast_enabled(N, D) && p.kcap <= KNN_WIDE_MAX_KCAP && N >= 4 * 256;
     if (wide) p.tile_rows = 256;
     const int64_t T = ceil_div(N, p.tile_rows);
     const int64_t sample_tiles = ceil_div(ceil_div(N, TB), stride);          // the sampled pre-pass stays on the 128-row engine
@@ -1007,9 +970,7 @@ static KnnPlan plan_knn(int64_t N, int64_t M, int D, int k, bool self, bool part
     // (and every row when a window cannot even fill a quarter of the GPU) get the sampled bound.  This is a
     // PERFORMANCE heuristic only: a row that meets a mirrored test with no bound yet floods its candidate
     // buffer, overflows, and is recomputed exactly by knn_fixup_kernel.
-    static const int pre_env = env_int("AM_KNN_SYM_PRE_WINDOWS", 0);
-    if (pre_env > 0) p.pre_windows = pre_env;
-    else if (p.per_win < 256) p.pre_windows = p.nwin;
+    if (p.per_win < 256) p.pre_windows = p.nwin;
     else p.pre_windows = std::min<int>(p.nwin, (int)ceil_div(512, p.per_win) + 2);
     p.nchunks = p.nwin;                               // partial-list slots
     // expected survivors per workgroup when only the sample bound is known:
@@ -1088,64 +1049,6 @@ static int run_knn(const float* X, int64_t N, int64_t ldx, const float* Y, int64
     // 2) half of the tile pairs + mirrored candidates, 3) merge, 4) exact fix-up of overflowed rows
     rc = launch_knn_sym<KCAP>(X, N, ldx, b.xn, b.thr, D, k1, p.win_tiles, p.nwin, p.per_win, b.partial, b.cand, b.cnt, p.cap,
                               b.wgq, p.qcap, b.wgq_count, b.ov_list, b.ov_count, out_r, st);
-#ifdef AM_DEV_KNOBS
-    static const int debug = env_int("AM_KNN_DEBUG", 0);
-    if (rc == AM_OK && debug) {                      // development aid: candidate statistics (synchronises!)
-        std::vector<int> cnt(N + 1);
-        const size_t nwg = (size_t)p.nwin * p.per_win;
-        std::vector<int> wq(nwg);
-        (void)hipStreamSynchronize(st);
-        (void)hipMemcpy(cnt.data(), b.cnt, (N + 1) * sizeof(int), hipMemcpyDeviceToHost);
-        (void)hipMemcpy(wq.data(), b.wgq_count, nwg * sizeof(int), hipMemcpyDeviceToHost);
-        long long tot = 0, mx = 0, wtot = 0, wmx = 0, wfull = 0;
-        for (int64_t i = 0; i < N; ++i) { tot += cnt[i]; mx = std::max<long long>(mx, cnt[i]); }
-        for (size_t i = 0; i < nwg; ++i) { wtot += wq[i]; wmx = std::max<long long>(wmx, wq[i]); wfull += wq[i] >= p.qcap; }
-        {
-            const int64_t rows_per_win = (int64_t)p.win_tiles * TB;
-            fprintf(stderr, "[am knn sym] mean candidates per row, by window of the row:");
-            for (int w = 0; w < p.nwin; ++w) {
-                long long t2 = 0, n2 = 0;
-                for (int64_t i = w * rows_per_win; i < std::min<int64_t>(N, (w + 1) * rows_per_win); ++i) { t2 += cnt[i]; ++n2; }
-                fprintf(stderr, " %.0f", n2 ? (double)t2 / n2 : 0.0);
-            }
-            fprintf(stderr, "\n");
-            std::vector<float> th(N), rr(N);
-            (void)hipMemcpy(th.data(), b.thr, N * sizeof(float), hipMemcpyDeviceToHost);
-            (void)hipMemcpy(rr.data(), out_r, N * sizeof(float), hipMemcpyDeviceToHost);
-            {
-                std::vector<float> pl((size_t)p.nwin * N * p.kcap);
-                (void)hipMemcpy(pl.data(), b.partial, pl.size() * sizeof(float), hipMemcpyDeviceToHost);
-                double acc2 = 0; long long finite = 0;
-                for (int64_t i = 0; i < N; ++i) {
-                    std::vector<float> all;
-                    for (int w = 0; w < p.nwin; ++w)
-                        for (int s2 = 0; s2 < p.kcap; ++s2) {
-                            const float v = pl[((size_t)w * N + i) * p.kcap + s2];
-                            if (std::isfinite(v)) { all.push_back(v); ++finite; }
-                        }
-                    std::sort(all.begin(), all.end());
-                    const float cum = (int)all.size() >= k1 ? all[k1 - 1] : INFINITY;
-                    acc2 += (th[i] - cum) / cum;
-                }
-                fprintf(stderr, "[am knn sym] lane-local lists: %.1f finite entries per row; mean (final bound - cumulative)/cumulative x1e4 = %.2f\n",
-                        (double)finite / N, 1e4 * acc2 / N);
-            }
-            fprintf(stderr, "[am knn sym] mean (final bound - r2)/r2 by window, x1e4:");
-            for (int w = 0; w < p.nwin; ++w) {
-                double t2 = 0; long long n2 = 0;
-                for (int64_t i = w * rows_per_win; i < std::min<int64_t>(N, (w + 1) * rows_per_win); ++i) {
-                    const double r2 = (double)rr[i] * rr[i];
-                    t2 += (th[i] - r2) / r2; ++n2; }
-                fprintf(stderr, " %.1f", n2 ? 1e4 * t2 / n2 : 0.0);
-            }
-            fprintf(stderr, "\n");
-        }
-        fprintf(stderr, "[am knn sym] N=%lld k1=%d windows=%d stride=%d cap=%d qcap=%d | candidates/row mean %.1f max %lld | "
-                        "overflow rows %d | wg queue mean %.1f max %lld full %lld of %zu\n",
-                (long long)N, k1, p.nchunks, p.pre_stride, p.cap, p.qcap, (double)tot / N, mx, cnt[N], (double)wtot / nwg, wmx,
-                wfull, nwg);
-    }
-#endif
     return rc;
 }
 
@@ -1350,7 +1253,7 @@ __global__ void __launch_bounds__(256) narrow64_kernel(const double* __restrict_
 }
 
 bool prdc64_filter_eligible(int64_t Nr, int64_t Nc, int D) {
-    return Nr >= 1 && Nc >= 1 && cross_fast_enabled(Nr, Nc, D) && plan_cross_fast(Nr, Nc, D).wide;
+    return Nr >= 1 && Nc >= 1 && cross_fast_enabled(Nr, Nc, D);
 }
 
 struct Prdc64Layout {
@@ -1449,7 +1352,7 @@ extern "C" int am_filter_stats_enable(int64_t* device_slots) {
 }
 
 // which form am_knn_radii_f32 / am_prdc_counts_f32 take for a shape: 0 exact general, 1 exact symmetric,
-// 2 f16 filter + verify on the 128 x 128 engine, 3 the same on the 256 x 256 engine
+// 2 f16 filter + verify on the 128 x 128 engine (k-NN only), 3 the same on the 256 x 256 engine
 extern "C" int am_knn_path(int64_t N, int64_t M, int D, int k, int self) {
     if (N < 1 || M < 1 || D < 1 || k < 1) return -1;
     if (k > AM_MAX_K) return 4;                     // row-at-a-time kernel (knn_rows_kernel)
@@ -1458,8 +1361,7 @@ extern "C" int am_knn_path(int64_t N, int64_t M, int D, int k, int self) {
 }
 extern "C" int am_prdc_path(int64_t Nr, int64_t Nc, int D) {
     if (Nr < 1 || Nc < 1 || D < 1) return -1;
-    if (!cross_fast_enabled(Nr, Nc, D)) return 0;
-    return plan_cross_fast(Nr, Nc, D).wide ? 3 : 2;
+    return cross_fast_enabled(Nr, Nc, D) ? 3 : 0;
 }
 
 // which of the two 256-row engines multiplies the tiles of a path-3 filter pass for rows of D elements (benchmark support:

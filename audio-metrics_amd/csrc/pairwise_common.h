@@ -513,10 +513,6 @@ int launch_knn_pstat(int kcap, unsigned nwg, const float* Xb, int64_t N, int64_t
                      uint2* wgq, float* wgv, int qcap, int* wgq_count, int part, int nparts, float fc, uint2* ovq, float* ovv,
                      unsigned long long* ovn, int ovcap, const int* skip, int* region_counter, hipStream_t st);
 // which of the two 256-row engines multiplies the tiles of the main filter passes: a pure function of the row length
-// (AM_WIDE_STATIONARY=0 in the A/B build: wide_engine.h for every shape)
-static inline bool wide_stationary(int Dh) {
-    static const int on = env_int("AM_WIDE_STATIONARY", 1);
-    return on != 0 && pstat_supported(Dh);
-}
+static inline bool wide_stationary(int Dh) { return pstat_supported(Dh); }
 
 }  // namespace am

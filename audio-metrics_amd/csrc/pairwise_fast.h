@@ -204,23 +204,6 @@ static int norms_of(const PreparedSet* prep, const float* X, int64_t N, int64_t 
     return launch_norms(X, N, ld, D, out, st);
 }
 
-// The exact engine's value for one pair: f32 fmaf chain over the inner index in the order 8c+0, 8c+4, 8c+1, ...
-// (tile_engine.h, "K order"); xs = the row held in LDS, zero-padded to a multiple of 8.
-__device__ __forceinline__ float exact_pair_dot(const float* __restrict__ xs, const float* __restrict__ y, int D) {
-    float acc = 0.f;
-    const int dp = (D + 7) / 8 * 8;
-    for (int c = 0; c < dp; c += 8) {
-        const f32x4 y0 = load_k4(y, c, D), y1 = load_k4(y, c + 4, D);
-        const f32x4 x0 = *reinterpret_cast<const f32x4*>(xs + c), x1 = *reinterpret_cast<const f32x4*>(xs + c + 4);
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            acc = fmaf(y0[s], x0[s], acc);
-            acc = fmaf(y1[s], x1[s], acc);
-        }
-    }
-    return acc;
-}
-
 // ------------------------------------------------------------------------------------------------
 // Membership counts, filter pass.  P rows = reference rows i (lane-local), Q rows = candidate rows j.
 // With G = the largest squared row norm of either set, E_i = fast_c (|r_i|^2 + G) and E'_j = fast_c (G + |c_j|^2)  (>= eps of every pair),
@@ -232,82 +215,53 @@ __device__ __forceinline__ float exact_pair_dot(const float* __restrict__ xs, co
 //   row minimum     a <= m_i + 2 E_i  QUEUED, m_i = an upper bound of min_j max(a_ij, 0) over the columns seen so
 //                   far (global array, atomicMin): the true minimiser j* has
 //                   a_ij* <= t_ij* + eps <= t_ij + eps <= max(a_ij, 0) + 2 eps for every j.
-// A queue entry is (i, j | COUNTED) - COUNTED = the pair was already counted as certain.  PRE = sampled
-// pre-pass (every qstride-th column tile): only m_i and the certain "any" flags are produced.
-constexpr int FAST_AUX_FLOATS = 6 * TB;                                    // LDS [2][3][128]
-constexpr size_t FAST_LDS_BYTES = (ENGINE_LDS_FLOATS + FAST_AUX_FLOATS) * sizeof(float) + 16;
+// A queue entry is (i, j | COUNTED) - COUNTED = the pair was already counted as certain.  The main passes are
+// cross_pstat*_kernel / cross_wide_kernel (wide_kernels.h).  Here: the sampled pre-pass of a call that wants the row
+// minimum (every qstride-th column tile, 128-row engine): only m_i and the certain "any" flags are produced.
+// Dynamic LDS: PAIRWISE_LDS_BYTES (the engine's stages + the [2][2][128] side data).
 
-struct CrossFastEpilogue {
+struct CrossMinSampleEpilogue {
     const float* qnorm;
     const float* qthr;
     int64_t nq;
     float fc;                   // fast_c(D)
     float rnmax_c;              // fast_c * G
-    float* aux;                 // LDS [2][3][128] : |c_j|^2, T'_j + E'_j, T'_j - E'_j of the tile
-    int32_t* col_count;
-    uint2* wgq;                 // this workgroup's append region
-    int* qn;                    // LDS slot counter
-    int qcap;
-    uint2* ovq;                 // global overflow queue
-    int* ov_count;
-    int ovcap;
-    int* fail;
-    int dbg;
+    float* aux;                 // LDS [2][2][128] : |c_j|^2, T'_j - E'_j of the tile
     float dsc;                  // -2 / (operand scales)
-    int64_t prow[2];
-    float xn[2], thi[2], tlo[2], e2[2], m[2];
-    bool rowok[2], anyf[2], covf[2];
-    float aux_n, aux_hi, aux_lo;
+    float xn[2], m[2];
+    bool anyf[2];
+    float aux_n, aux_lo;
     const LaneInfo& L;
 
-    __device__ __forceinline__ CrossFastEpilogue(const LaneInfo& l) : L(l) {}
-    __device__ __forceinline__ void push(int64_t i, unsigned jflag) {
-        const int slot = atomicAdd(qn, 1);
-        if (slot < qcap) {
-            wgq[slot] = make_uint2((unsigned)i, jflag);
-        } else if (*reinterpret_cast<volatile int*>(fail) == 0) {   // region full: spill to the global queue
-            // (once the fail flag is up nothing is counted any more: on inputs the bound cannot decide - e.g. sets three
-            // orders of magnitude apart - billions of pairs arrive here and would wrap the counter)
-            const unsigned s2 = atomicAdd(reinterpret_cast<unsigned*>(ov_count), 1u);
-            if (s2 < (unsigned)ovcap) ovq[s2] = make_uint2((unsigned)i, jflag);
-            else *fail = 1;                                 // -> the exact kernel redoes the whole call
-        }
-    }
+    __device__ __forceinline__ CrossMinSampleEpilogue(const LaneInfo& l) : L(l) {}
     __device__ __forceinline__ void aux_issue(int, int64_t qtile) {
         if (L.tid < TB) {
             const int64_t j = qtile * TB + L.tid;
             if (j < nq) {
-                const float e = fmaf(fc, qnorm[j], rnmax_c);
                 aux_n = qnorm[j];
-                aux_hi = qthr[j] + e;
-                aux_lo = qthr[j] - e;
+                aux_lo = qthr[j] - fmaf(fc, qnorm[j], rnmax_c);
             } else {
                 aux_n = INFINITY;                           // a = +inf: never below anything
-                aux_hi = -INFINITY;
                 aux_lo = -INFINITY;
             }
         }
     }
     __device__ __forceinline__ void aux_commit(int t) {
         if (L.tid < TB) {
-            float* d = aux + (t & 1) * 3 * TB + L.tid;
+            float* d = aux + (t & 1) * 2 * TB + L.tid;
             d[0] = aux_n;
-            d[TB] = aux_hi;
-            d[2 * TB] = aux_lo;
+            d[TB] = aux_lo;
         }
     }
-    template <bool PRE, bool WANT_MIN>
-    __device__ __forceinline__ void finish_impl(int t, int64_t qtile, f32x16 (&acc)[2][2]) {
-        const float* a = aux + (t & 1) * 3 * TB + L.wm * 64 + L.h * 4;
-        const int64_t jbase = qtile * TB + L.wm * 64 + L.h * 4;
-        if (dbg & 8) return;                                   // timing experiment: MFMA pipeline only
+    __device__ __forceinline__ void finish(int t, int64_t, f32x16 (&acc)[2][2]) {
+        const float* a = aux + (t & 1) * 2 * TB + L.wm * 64 + L.h * 4;
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt) {
             f32x4 yn[4], th[4];
 #pragma unroll
             for (int g4 = 0; g4 < 4; ++g4) {
                 yn[g4] = *reinterpret_cast<const f32x4*>(a + mt * 32 + g4 * 8);
-                th[g4] = *reinterpret_cast<const f32x4*>(a + (PRE ? 2 : 1) * TB + mt * 32 + g4 * 8);   // PRE: T'-E', main: T'+E'
+                th[g4] = *reinterpret_cast<const f32x4*>(a + TB + mt * 32 + g4 * 8);
             }
 #pragma unroll
             for (int nt = 0; nt < 2; ++nt) {
@@ -318,125 +272,55 @@ struct CrossFastEpilogue {
                     tmin = fminf(tmin, u);
                     marg = fminf(marg, u - th[reg >> 2][reg & 3]);          // +inf - (-inf) = +inf past nq
                 }
-                if constexpr (WANT_MIN) m[nt] = fminf(m[nt], fmaxf(tmin, 0.f));
-                if constexpr (PRE) {
-                    anyf[nt] = anyf[nt] || (marg < 0.f);                     // some a < T'_j - E'_j
-                } else {
-                    const float prow_thr = WANT_MIN ? fmaxf(thi[nt], m[nt] + e2[nt]) : thi[nt];
-                    if (!(dbg & 4) && __any(rowok[nt] && (tmin <= prow_thr || (!anyf[nt] && marg <= 0.f)))) {
-                        const float* alo = a + 2 * TB + mt * 32;
-#pragma unroll
-                        for (int reg = 0; reg < 16; ++reg) {
-                            const float u = fmaf(dsc, acc[mt][nt][reg], xn[nt] + yn[reg >> 2][reg & 3]);
-                            const int64_t j = jbase + mt * 32 + (reg >> 2) * 8 + (reg & 3);
-                            const bool sure = rowok[nt] && u < tlo[nt];
-                            const unsigned long long mask = __ballot(sure);
-                            if (mask != 0ull && L.lane == 0) {               // lanes 0-31: column j, lanes 32-63: column j + 4
-                                const int lo = __popcll(mask & 0xffffffffull);
-                                const int hi = __popcll(mask >> 32);
-                                if (lo) atomicAdd(col_count + j - L.h * 4, lo);
-                                if (hi) atomicAdd(col_count + j - L.h * 4 + 4, hi);
-                            }
-                            covf[nt] = covf[nt] || sure;                              // inside for certain: the row is covered
-                            bool want = rowok[nt] && !sure && u <= thi[nt];           // ambiguous count
-                            if constexpr (WANT_MIN) want = want || (rowok[nt] && u <= m[nt] + e2[nt]);   // row-minimum candidate
-                            if (rowok[nt] && !anyf[nt] && u <= th[reg >> 2][reg & 3]) {
-                                if (u < alo[(reg >> 2) * 8 + (reg & 3)]) { anyf[nt] = true; if (dbg & 1) want = true; }   // certain witness
-                                else want = true;                                     // ambiguous "any"
-                            }
-                            if (want) push(prow[nt], (unsigned)j | (sure ? FAST_COUNTED : 0u));
-                        }
-                    }
-                }
+                m[nt] = fminf(m[nt], fmaxf(tmin, 0.f));
+                anyf[nt] = anyf[nt] || (marg < 0.f);                         // some a < T'_j - E'_j
             }
         }
     }
 };
 
-template <bool PRE, bool WANT_MIN>
-struct CrossFastShim {            // picks the epilogue body at compile time
-    CrossFastEpilogue& e;
-    __device__ __forceinline__ void aux_issue(int t, int64_t q) { e.aux_issue(t, q); }
-    __device__ __forceinline__ void aux_commit(int t) { e.aux_commit(t); }
-    __device__ __forceinline__ void finish(int t, int64_t q, f32x16 (&acc)[2][2]) {
-        e.template finish_impl<PRE, WANT_MIN>(t, q, acc);
-    }
-};
-
-// Rb / Cb: f16 copies viewed as f32 words (ld and Dh in words, Dh % 32 == 0).
-template <bool PRE, bool WANT_MIN>
+// Rb / Cb: f16 copies viewed as f32 words (ld and Dh in words, Dh % 32 == 0).  Grid: row blocks x nchunks, with
+// nchunks <= the number of sampled tiles (plan_cross_fast), so every workgroup has at least one tile.
 __global__ void __launch_bounds__(ENGINE_THREADS, 2)
-cross_fast_kernel(const float* __restrict__ Rb, int64_t Nr, int64_t ldr, const float* __restrict__ rnorm,
-                  const float* __restrict__ rthr, const float* __restrict__ Cb, int64_t Nc, int64_t ldc,
-                  const float* __restrict__ cnorm, const float* __restrict__ cthr, int Dh, int nchunks, int qstride,
-                  const unsigned* __restrict__ maxn, unsigned* __restrict__ rmin_approx, unsigned* __restrict__ row_any,
-                  unsigned* __restrict__ row_cover, int32_t* __restrict__ col_count, uint2* __restrict__ wgq, int qcap, int* __restrict__ wgq_count,
-                  uint2* __restrict__ ovq, int* __restrict__ ov_count, int ovcap, int* __restrict__ fail, int dbg, float fc,
-                  int grp_rows) {
+cross_min_sample_kernel(const float* __restrict__ Rb, int64_t Nr, int64_t ldr, const float* __restrict__ rnorm,
+                        const float* __restrict__ Cb, int64_t Nc, int64_t ldc, const float* __restrict__ cnorm,
+                        const float* __restrict__ cthr, int Dh, int nchunks, int qstride, const unsigned* __restrict__ maxn,
+                        unsigned* __restrict__ rmin_approx, unsigned* __restrict__ row_any, int* __restrict__ fail, float fc) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const LaneInfo L;
     const int64_t q_tiles = ((Nc + TB - 1) / TB + qstride - 1) / qstride;
-    const WorkItem w = grp_rows > 0 ? work_item_grouped(q_tiles, nchunks, (Nr + TB - 1) / TB, grp_rows) : work_item(q_tiles, nchunks);
-    if (w.ntiles == 0) {                                   // padding item of the grouped grid
-        if (!PRE && L.tid == 0) wgq_count[blockIdx.x] = 0;
-        return;
-    }
-    int* qn = reinterpret_cast<int*>(lds + ENGINE_LDS_FLOATS + FAST_AUX_FLOATS);
-    if (L.tid == 0) *qn = 0;
+    const WorkItem w = work_item(q_tiles, nchunks);
 
     const float gmax = fmaxf(__uint_as_float(maxn[0]), __uint_as_float(maxn[1]));
-    CrossFastEpilogue epi(L);
+    CrossMinSampleEpilogue epi(L);
     epi.fc = fc;
     epi.qnorm = cnorm;
     epi.qthr = cthr;
     epi.nq = Nc;
     epi.rnmax_c = fc * gmax;
     epi.aux = lds + ENGINE_LDS_FLOATS;
-    epi.col_count = col_count;
-    epi.wgq = wgq + (int64_t)blockIdx.x * qcap;
-    epi.qn = qn;
-    epi.qcap = qcap;
-    epi.ovq = ovq;
-    epi.ov_count = ov_count;
-    epi.ovcap = ovcap;
-    epi.fail = fail;
-    epi.dbg = dbg;
     epi.dsc = half_unscale(maxn[2], maxn[3]);
+    // (operands that cannot be scaled: the exact kernel takes the whole call)
     if (blockIdx.x == 0 && L.tid == 0 && !(half_scale_ok(maxn[2]) && half_scale_ok(maxn[3]))) *fail = 1;
+    int64_t prow[2];
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) {
-        const int64_t i = w.prow0 + L.wn * 64 + nt * 32 + L.r;
-        const bool ok = i < Nr;
-        epi.prow[nt] = i;
-        epi.rowok[nt] = ok;
-        epi.xn[nt] = ok ? rnorm[i] : 0.f;
-        const float e = fc * ((ok ? rnorm[i] : 0.f) + gmax);
-        epi.thi[nt] = ok ? rthr[i] + e : -INFINITY;
-        epi.tlo[nt] = ok ? rthr[i] - e : -INFINITY;
-        epi.e2[nt] = 2.f * e;
-        epi.m[nt] = (WANT_MIN && ok) ? __uint_as_float(rmin_approx[i]) : INFINITY;
-        epi.anyf[nt] = ok ? (row_any[i] != 0u && !(dbg & 2)) : true;
-        epi.covf[nt] = false;
+        prow[nt] = w.prow0 + L.wn * 64 + nt * 32 + L.r;
+        const bool ok = prow[nt] < Nr;
+        epi.xn[nt] = ok ? rnorm[prow[nt]] : 0.f;
+        epi.m[nt] = ok ? __uint_as_float(rmin_approx[prow[nt]]) : INFINITY;
+        epi.anyf[nt] = ok ? row_any[prow[nt]] != 0u : true;
     }
-    CrossFastShim<PRE, WANT_MIN> shim{epi};
     dense_pipeline_early<EV_FAST, false>(Cb, Nc, ldc, LinearTiles{w.qtile0, qstride}, Rb, Nr, ldr, w.prow0, w.ntiles, Dh,
-                                         lds, L, shim);
+                                         lds, L, epi);
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) {
         const float mn = fminf(epi.m[nt], __shfl_xor(epi.m[nt], 32));
         const int other = __shfl_xor((int)epi.anyf[nt], 32);                  // unconditionally: every lane must take part
-        const int other_c = __shfl_xor((int)epi.covf[nt], 32);
-        const bool any = epi.anyf[nt] || other != 0;
-        const bool cov = epi.covf[nt] || other_c != 0;
-        if (L.h == 0 && epi.rowok[nt]) {
-            if constexpr (WANT_MIN) atomicMin(rmin_approx + epi.prow[nt], __float_as_uint(mn));   // mn >= 0: uint order == float order
-            if (any) atomicOr(row_any + epi.prow[nt], 1u);
-            if (cov) atomicOr(row_cover + epi.prow[nt], 1u);
+        if (L.h == 0 && prow[nt] < Nr) {
+            atomicMin(rmin_approx + prow[nt], __float_as_uint(mn));           // mn >= 0: uint order == float order
+            if (epi.anyf[nt] || other != 0) atomicOr(row_any + prow[nt], 1u);
         }
-    }
-    if constexpr (!PRE) {
-        __syncthreads();
-        if (L.tid == 0) wgq_count[blockIdx.x] = *qn < qcap ? *qn : qcap;
     }
 }
 
@@ -539,87 +423,6 @@ __global__ void __launch_bounds__(256) cross_verify_regions_kernel(const float* 
             if (any) atomicOr(row_any + i, 1u);
             if (cov) atomicOr(row_cover + i, 1u);
         }
-    }
-}
-
-// Verification of one workgroup region (same grid as the filter pass): the entries are bucketed by reference
-// row in LDS, then each wave takes rows - the row goes to LDS once, every lane evaluates one candidate with the
-// exact engine's fmaf chain - and the exact reductions are applied.
-__global__ void __launch_bounds__(256) cross_verify_kernel(const float* __restrict__ R, int64_t Nr, int64_t ldr,
-                                                           const float* __restrict__ rnorm, const float* __restrict__ rthr,
-                                                           const float* __restrict__ C, int64_t ldc,
-                                                           const float* __restrict__ cnorm, const float* __restrict__ cthr, int D,
-                                                           int nchunks, int grp_rows, const uint2* __restrict__ wgq, int qcap,
-                                                           const int* __restrict__ wgq_count, int32_t* __restrict__ col_count,
-                                                           unsigned* __restrict__ row_min_bits, unsigned* __restrict__ row_any,
-                                                           unsigned* __restrict__ row_cover) {
-    extern __shared__ __attribute__((aligned(16))) float vlds[];       // [4][dp] rows, then qcap sorted entries
-    __shared__ int bucket[TB], start[TB];
-    const int n = wgq_count[blockIdx.x];
-    if (n == 0) return;
-    const int dp = (D + 7) / 8 * 8;
-    unsigned* sorted = reinterpret_cast<unsigned*>(vlds + 4 * dp);
-    const uint2* q = wgq + (int64_t)blockIdx.x * qcap;
-    // row block of this region: the filter kernel's work mapping (q_tiles is irrelevant for prow0)
-    const int64_t prow0 = grp_rows > 0 ? work_item_grouped(1, nchunks, (Nr + TB - 1) / TB, grp_rows).prow0
-                                       : (int64_t)(blockIdx.x / nchunks) * TB;
-    if (threadIdx.x < TB) bucket[threadIdx.x] = 0;
-    __syncthreads();
-    constexpr int PER = 8;                                             // qcap <= 256 * PER
-    int pos[PER];
-#pragma unroll
-    for (int s = 0; s < PER; ++s) {
-        const int e = threadIdx.x + s * 256;
-        pos[s] = e < n ? atomicAdd(&bucket[(int)(q[e].x - prow0)], 1) : 0;
-    }
-    __syncthreads();
-    if (threadIdx.x < 64) {                                            // exclusive scan of the 128 bucket sizes
-        const int a0 = bucket[2 * threadIdx.x], a1 = bucket[2 * threadIdx.x + 1];
-        int v = a0 + a1;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int o = __shfl_up(v, off);
-            if ((int)threadIdx.x >= off) v += o;
-        }
-        start[2 * threadIdx.x] = v - a0 - a1;
-        start[2 * threadIdx.x + 1] = v - a1;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int s = 0; s < PER; ++s) {
-        const int e = threadIdx.x + s * 256;
-        if (e < n) sorted[start[(int)(q[e].x - prow0)] + pos[s]] = q[e].y;
-    }
-    __syncthreads();
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    float* xs = vlds + wave * dp;
-    for (int lr = wave; lr < TB; lr += 4) {
-        const int cnt = bucket[lr];
-        if (cnt == 0) continue;
-        const int64_t i = prow0 + lr;
-        for (int k = lane; k < dp; k += 64) xs[k] = k < D ? R[i * ldr + k] : 0.f;
-        __builtin_amdgcn_wave_barrier();                               // same wave wrote the row: LDS ops stay in order
-        const float xi = rnorm[i], ti = rthr[i];
-        float mn = INFINITY;
-        bool any = false, cov = false;
-        for (int e0 = 0; e0 < cnt; e0 += 64) {
-            const int e = e0 + lane;
-            if (e < cnt) {
-                const unsigned jf = sorted[start[lr] + e];
-                const int64_t j = jf & ~FAST_COUNTED;
-                const float t = clamp0(fmaf(-2.f, exact_pair_dot(xs, C + j * ldc, D), xi + cnorm[j]));
-                cross_apply(t, j, jf, ti, cthr, col_count, mn, any, cov);
-            }
-        }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) mn = fminf(mn, __shfl_xor(mn, off));
-        const bool wave_any = __any(any), wave_cov = __any(cov);
-        if (lane == 0) {
-            if (row_min_bits != nullptr) atomicMin(row_min_bits + i, __float_as_uint(mn));   // t >= 0: uint order == float order
-            if (wave_any) atomicOr(row_any + i, 1u);
-            if (wave_cov) atomicOr(row_cover + i, 1u);
-        }
-        __builtin_amdgcn_wave_barrier();
     }
 }
 
@@ -751,68 +554,58 @@ __global__ void __launch_bounds__(256) cross_fail_reset_kernel(const int* __rest
     }
 }
 
+// The regions of the 256-row engines are verified in batches of 64: 4096 entries each, so that a few candidate columns that
+// EVERY reference row has to look at exactly - a block of identical low-norm rows, silence in a stem dataset, is
+// everybody's nearest neighbour at one and the same distance - stay in the regions (coalesced verification) instead of
+// spilling into the one-pair-per-thread overflow path (tools/dups_probe.py)
+constexpr int CROSS_FAST_QCAP = 4096;
+constexpr int CROSS_FAST_OVCAP = 1 << 22;
+
 struct CrossFastPlan {
     int nchunks, pre_chunks, qstride, qcap, ovcap, grp_rows;
     int64_t blocks;
-    bool wide;                  // main pass on the 256 x 256 engine (cross_wide_kernel)
 };
 
 static CrossFastPlan plan_cross_fast(int64_t Nr, int64_t Nc, int D) {
     CrossFastPlan p;
-    p.nchunks = choose_chunks(Nr, Nc);
-    static const int grp = env_int("AM_FAST_GROUP_ROWS", 8);                     // 0: plain (row block, chunk) order
-    p.grp_rows = (grp == 1 || grp == 2 || grp == 4 || grp == 8 || grp == 16 || grp == 32 || grp == 64) ? grp : 0;
-    p.blocks = p.grp_rows > 0 ? cross_grouped_blocks(ceil_div(Nr, TB), p.nchunks, p.grp_rows) : ceil_div(Nr, TB) * p.nchunks;
-    static const int wide = env_int("AM_FAST_WIDE", 1);
-    p.wide = wide != 0;
-    if (p.wide) {
-        // Row blocks of a group (the 32 workgroups of an XCD = grp_rows row blocks x 32 / grp_rows column chunks).  wide_engine.h
-        // streams the P blocks too: eight of them (2 MB of f16) stay in an XCD's L2 beside the Q window.  The stationary
-        // engines hold P in registers - the L2 only serves Q - so ALL 32 workgroups walk ONE column chunk: every Q tile is
-        // fetched once per 32 row blocks instead of once per 8 (100 000 x 512: 9.22 / 8.87 / 8.79 / 8.54 ms per launch at
-        // 4 / 8 / 16 / 32, CLAP-shaped k = 10 10.56 -> 10.14; D = 128 flat; profiles/r6/wide_bench_cross_group.txt).
-        static const int wgrp_env = env_int("AM_WIDE_GROUP_ROWS", 0);
-        const int wgrp = wgrp_env > 0 ? wgrp_env : (wide_stationary((int)(half_ld(D) / 2)) ? 32 : 8);
-        static const int wtarget = env_int("AM_WIDE_WG_TARGET", 6144);               // ~24 rounds of 256 CUs x 1 workgroup
-        p.grp_rows = (wgrp == 1 || wgrp == 2 || wgrp == 4 || wgrp == 8 || wgrp == 16 || wgrp == 32) ? wgrp : 8;
-        const int grp_chunks = 32 / p.grp_rows;
-        const int64_t rbw = ceil_div(Nr, WIDE_TILE_ROWS), qtw = ceil_div(Nc, WIDE_TILE_ROWS);
-        int64_t want = std::max<int64_t>(ceil_div(wtarget, rbw), 1);
-        want = ceil_div(want, grp_chunks) * grp_chunks;
-        // at least ~8 column tiles per workgroup (row shards of a multi-GPU run would otherwise get 3-tile work items
-        // whose pipeline fill and epilogue set-up dominate)
-        want = std::min<int64_t>(want, std::max<int64_t>(qtw / 8 / grp_chunks * grp_chunks, grp_chunks));
-        want = std::min<int64_t>(want, std::max<int64_t>(qtw / grp_chunks * grp_chunks, 1));
-        want = std::min<int64_t>(want, qtw);
-        p.nchunks = (int)want;
-        p.blocks = wide_grouped_blocks(rbw, p.nchunks, p.grp_rows);
-    }
+    // Row blocks of a group (the 32 workgroups of an XCD = grp_rows row blocks x 32 / grp_rows column chunks).  wide_engine.h
+    // streams the P blocks too: eight of them (2 MB of f16) stay in an XCD's L2 beside the Q window.  The stationary
+    // engines hold P in registers - the L2 only serves Q - so ALL 32 workgroups walk ONE column chunk: every Q tile is
+    // fetched once per 32 row blocks instead of once per 8 (100 000 x 512: 9.22 / 8.87 / 8.79 / 8.54 ms per launch at
+    // 4 / 8 / 16 / 32, CLAP-shaped k = 10 10.56 -> 10.14; D = 128 flat; profiles/r6/wide_bench_cross_group.txt).
+    static const int wgrp_env = env_int("AM_WIDE_GROUP_ROWS", 0);
+    const int wgrp = wgrp_env > 0 ? wgrp_env : (wide_stationary((int)(half_ld(D) / 2)) ? 32 : 8);
+    static const int wtarget = env_int("AM_WIDE_WG_TARGET", 6144);               // ~24 rounds of 256 CUs x 1 workgroup
+    p.grp_rows = (wgrp == 1 || wgrp == 2 || wgrp == 4 || wgrp == 8 || wgrp == 16 || wgrp == 32) ? wgrp : 8;
+    const int grp_chunks = 32 / p.grp_rows;
+    const int64_t rbw = ceil_div(Nr, WIDE_TILE_ROWS), qtw = ceil_div(Nc, WIDE_TILE_ROWS);
+    int64_t want = std::max<int64_t>(ceil_div(wtarget, rbw), 1);
+    want = ceil_div(want, grp_chunks) * grp_chunks;
+    // at least ~8 column tiles per workgroup (row shards of a multi-GPU run would otherwise get 3-tile work items
+    // whose pipeline fill and epilogue set-up dominate)
+    want = std::min<int64_t>(want, std::max<int64_t>(qtw / 8 / grp_chunks * grp_chunks, grp_chunks));
+    want = std::min<int64_t>(want, std::max<int64_t>(qtw / grp_chunks * grp_chunks, 1));
+    want = std::min<int64_t>(want, qtw);
+    p.nchunks = (int)want;
+    p.blocks = wide_grouped_blocks(rbw, p.nchunks, p.grp_rows);
     // Sampled "any" pre-pass: every stride-th candidate tile.  16 until round 5; since the main pass's hit path got cheap (scalar
     // gates, accumulator start values) a witness found there costs little, and what the pre-pass is still good for - taking
     // the rows with MANY witnesses out of the "any" direction early - needs about six sampled tiles: at 100 000 x 512 stride
     // 16 / 32 / 64 / 128 / no pre-pass give 9.88 / 9.75 / 9.68 / 9.75 / 9.96 ms per call on the bench sets and 10.72 / 10.48 /
     // 10.47 / 10.32 / 10.29 ms on CLAP-shaped ones with k = 10 (profiles/r5/ab_pre_stride.txt); narrow rows are flat.
     static const int stride_env = env_int("AM_FAST_PRE_STRIDE", 0);
-    p.qstride = stride_env > 0 ? stride_env
-                               : (p.wide ? (int)std::min<int64_t>(std::max<int64_t>(ceil_div(Nc, WIDE_TILE_ROWS) / 6, 16), 64) : 16);
-    const int64_t sample_tiles = ceil_div(ceil_div(Nc, TB), p.qstride);
-    p.pre_chunks = (int)std::min<int64_t>(sample_tiles, 8);
-    static const int qcap = std::min(env_int("AM_FAST_QCAP", 2048), 2048);       // cross_verify_kernel: <= 256 * 8
-    static const int ovcap = env_int("AM_FAST_OVCAP", 1 << 22);
-    p.qcap = qcap;
-    // The 256-row engine's regions are verified in batches of 64 (no limit from a sort in LDS): twice the size, so that a
-    // few candidate columns that EVERY reference row has to look at exactly - a block of identical low-norm rows, silence in
-    // a stem dataset, is everybody's nearest neighbour at one and the same distance - stay in the regions (coalesced
-    // verification) instead of spilling into the one-pair-per-thread overflow path (tools/dups_probe.py)
-    if (p.wide && env_int("AM_FAST_QCAP", 0) == 0) p.qcap = 4096;
-    p.ovcap = ovcap;
+    p.qstride = stride_env > 0 ? stride_env : (int)std::min<int64_t>(std::max<int64_t>(ceil_div(Nc, WIDE_TILE_ROWS) / 6, 16), 64);
+    // column chunks of cross_min_sample_kernel (128-row tiles)
+    p.pre_chunks = (int)std::min<int64_t>(ceil_div(ceil_div(Nc, TB), p.qstride), 8);
+    p.qcap = CROSS_FAST_QCAP;
+    p.ovcap = CROSS_FAST_OVCAP;
     return p;
 }
 
 struct CrossFastBuffers {
     uint16_t *rb, *cb;
     unsigned *maxn, *rmin_approx;
-    uint2 *wgq, *ovq, *items;       // items: (region, first entry) per batch of 64 entries (wide path)
+    uint2 *wgq, *ovq, *items;       // items: (region, first entry) per batch of 64 entries
     int *wgq_count, *ov_count;      // ov_count[0] = overflow entries, ov_count[1] = fail flag, ov_count[2] = number of items
 };
 
@@ -830,6 +623,11 @@ static CrossFastBuffers carve_cross_fast(Carver& c, int64_t Nr, int64_t Nc, int 
     return b;
 }
 
+// Widest rows the membership filter takes.  Inherited from the LDS tile of the retired per-region verification kernel and
+// pinned by tests/test_gpu_wide_filter.py; nothing in the remaining kernels needs it (fast_c holds up to FAST_MAX_DIM).
+constexpr int CROSS_FAST_MAX_DIM = 3328;
+static_assert(CROSS_FAST_MAX_DIM <= FAST_MAX_DIM, "fast_c's derivation");
+
 static bool cross_fast_enabled(int64_t Nr, int64_t Nc, int D) {
     static const int on = env_int("AM_PRDC_FAST", 1);
     // Where the membership filter starts to pay (round 4: tools/threshold_sweep.py on randn, unit-norm and clustered sets,
@@ -839,8 +637,7 @@ static bool cross_fast_enabled(int64_t Nr, int64_t Nc, int D) {
     static const int min_pairs_env = env_int("AM_FAST_MIN_PAIRS_LOG2", 0);
     const int64_t min_pairs_n = min_pairs_env > 0 ? ((int64_t)1 << min_pairs_env)
                                                   : (D >= 256 ? (int64_t)1 << 24 : D >= 128 ? (int64_t)1 << 26 : D >= 32 ? (int64_t)100000000 : (int64_t)1 << 28);
-    const size_t verify_lds = (size_t)(4 * ((D + 7) / 8 * 8) + 2048) * sizeof(float);
-    return on != 0 && D >= FAST_MIN_DIM && D <= FAST_MAX_DIM && verify_lds <= 60 * 1024 && Nr * Nc >= min_pairs_n &&
+    return on != 0 && D >= FAST_MIN_DIM && D <= CROSS_FAST_MAX_DIM && Nr * Nc >= min_pairs_n &&
            Nr < ((int64_t)1 << 31) && Nc < ((int64_t)1 << 31);
 }
 
@@ -854,7 +651,7 @@ static int run_cross_fast(const float* R, int64_t Nr, int64_t ldr, const float* 
     int rc;
     // (float64 route: R, C are float32-rounded copies and rt, ct rounded thresholds; both roundings are priced into the band)
     const float fc = h64 != nullptr ? fast_c(D) + 3.814697265625e-06f : fast_c(D);
-    AM_REQUIRE(h64 == nullptr || (p.wide && !want_min), AM_ERR_BAD_ARG, "the float64 route is the 256-row form without row minima");
+    AM_REQUIRE(h64 == nullptr || !want_min, AM_ERR_BAD_ARG, "the float64 route is the form without row minima");
     AM_HIP_TRY(hipMemsetAsync(b.maxn, 0, 4 * sizeof(unsigned), st));
     AM_HIP_TRY(hipMemsetAsync(b.ov_count, 0, 4 * sizeof(int), st));
     if (prep_r != nullptr) hipLaunchKernelGGL(prepared_stats_kernel, dim3(1), dim3(64), 0, st, prep_r->stats, b.maxn, 0, 2, -1);
@@ -868,26 +665,14 @@ static int run_cross_fast(const float* R, int64_t Nr, int64_t ldr, const float* 
     const float* Rb = reinterpret_cast<const float*>(prep_r != nullptr ? prep_r->half : b.rb);
     const float* Cb = reinterpret_cast<const float*>(prep_c != nullptr ? prep_c->half : b.cb);
     int* fail = b.ov_count + 1;
-    {
-        const void* kernels[] = {reinterpret_cast<const void*>(&cross_fast_kernel<true, true>),
-                                 reinterpret_cast<const void*>(&cross_fast_kernel<true, false>),
-                                 reinterpret_cast<const void*>(&cross_fast_kernel<false, true>),
-                                 reinterpret_cast<const void*>(&cross_fast_kernel<false, false>)};
-        for (const void* k : kernels)
-            AM_HIP_TRY(ensure_dynamic_lds(k, (int)FAST_LDS_BYTES));
-    }
-    const int dbg = env_int("AM_FAST_DBG", 0);
-    // sampled pre-pass over every 16th column tile: certain "any" witnesses (and, when the row minimum is wanted,
+    // sampled pre-pass over every qstride-th column tile: certain "any" witnesses (and, when the row minimum is wanted,
     // an approximate minimum that bounds its candidate queue)
-    auto launch_filter = [&](auto kernel, unsigned grid, int nchunks, int qstride, int grp_rows) {
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(ENGINE_THREADS), FAST_LDS_BYTES, st, Rb, Nr, ldb / 2, rn, rt, Cb, Nc, ldb / 2,
-                           cn, ct, Dh, nchunks, qstride, b.maxn, b.rmin_approx, rany, rcov, col_count, b.wgq, p.qcap, b.wgq_count,
-                           b.ovq, b.ov_count, p.ovcap, fail, dbg, fc, grp_rows);
-    };
-    const unsigned pre_grid = (unsigned)(ceil_div(Nr, TB) * p.pre_chunks);
-    static const int pre_any = env_int("AM_FAST_PRE_ANY", 1);          // 1: on the engine of the main pass, 2: 128-row engine, 0: none
-    if (want_min) launch_filter(&cross_fast_kernel<true, true>, pre_grid, p.pre_chunks, p.qstride, 0);
-    else if (pre_any == 1 && p.wide) {
+    if (want_min) {
+        AM_HIP_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(&cross_min_sample_kernel), (int)PAIRWISE_LDS_BYTES));
+        hipLaunchKernelGGL(cross_min_sample_kernel, dim3((unsigned)(ceil_div(Nr, TB) * p.pre_chunks)), dim3(ENGINE_THREADS),
+                           PAIRWISE_LDS_BYTES, st, Rb, Nr, ldb / 2, rn, Cb, Nc, ldb / 2, cn, ct, Dh, p.pre_chunks, p.qstride, b.maxn,
+                           b.rmin_approx, rany, fail, fc);
+    } else {
         // chunks of the sampled tiles per row block: the count that needs the fewest tile-times on 256 CUs (rounds of
         // workgroups x tiles per workgroup, one tile-time of fill and drain per round)
         const int64_t samples = ceil_div(ceil_div(Nc, WIDE_TILE_ROWS), p.qstride), rbs = ceil_div(Nr, WIDE_TILE_ROWS);
@@ -903,49 +688,36 @@ static int run_cross_fast(const float* R, int64_t Nr, int64_t ldr, const float* 
         if ((rc = launch_cross_wide_sample(Rb, Nr, ldb / 2, rn, Cb, Nc, ldb / 2, cn, ct, Dh, p.qstride, chunks, b.maxn, rany, fc,
                                            st)) != AM_OK)
             return rc;
-    } else if (pre_any) launch_filter(&cross_fast_kernel<true, false>, pre_grid, p.pre_chunks, p.qstride, 0);
+    }
     AM_LAUNCH_CHECK();
     unsigned* rmin_or_null = want_min ? rmin : nullptr;
-    if (p.wide) {
-        // budgets of the data-dependent fallback (cross_fast_decide_kernel).  The overflow queue's budget is enforced INSIDE
-        // the filter pass: entries past it raise the fail flag at once and the workgroups not yet started return at their
-        // first instruction - on inputs the bound cannot decide most of the pass's time went into those entries
-        // (an overflow-queue entry costs ~20 ns in its one-pair-per-thread kernel, a pair of the exact kernel 2 D / 140 TF:
-        // the budget is what costs a quarter of the exact kernel's time)
-        const long long pairs = (long long)Nr * (long long)Nc;
-        const long long limit_total = std::max<long long>(pairs / 128, 65536);
-        const int limit_overflow = (int)std::min<long long>(std::max<long long>((pairs >> 22) * D, 65536), p.ovcap);
-        clock_begin(AM_KERNEL_PRDC_CROSS, st);
-        // rows of up to 512 f16: the operand-stationary engine (pstat_engine.h), wider ones: both operands through LDS
-        const auto launch_main = wide_stationary(Dh) ? &launch_cross_pstat : &launch_cross_wide;
-        if ((rc = launch_main(want_min, (unsigned)p.blocks, Rb, Nr, ldb / 2, rn, rt, Cb, Nc, ldb / 2, cn, ct, Dh, p.nchunks,
-                                    p.grp_rows, b.maxn, b.rmin_approx, rany, rcov, col_count, b.wgq, p.qcap, b.wgq_count, b.items,
-                                    b.ovq, b.ov_count, limit_overflow, fail, fc, st)) != AM_OK)
-            return rc;
-        clock_end(AM_KERNEL_PRDC_CROSS, st);
-        hipLaunchKernelGGL(cross_fast_decide_kernel, dim3(1), dim3(64), 0, st, b.ov_count, p.ovcap, fail, limit_total, limit_overflow);
-        clock_begin(AM_KERNEL_PRDC_VERIFY, st);
-        if (h64 != nullptr) {
-            hipLaunchKernelGGL(cross_verify_regions64_kernel, dim3(CROSS_VERIFY_GRID), dim3(256), 0, st, *h64, D, b.wgq, p.qcap, b.wgq_count,
-                               b.items, b.ov_count + 2, col_count, rany, rcov, fail);
-        } else {
-            AM_HIP_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(&cross_verify_regions_kernel), (int)VERIFY_LDS_BYTES));
-            hipLaunchKernelGGL(cross_verify_regions_kernel, dim3(CROSS_VERIFY_GRID), dim3(256), VERIFY_LDS_BYTES, st, R, ldr, rn, rt, C, ldc,
-                               cn, ct, D, b.wgq, p.qcap, b.wgq_count, b.items, b.ov_count + 2, col_count, rmin_or_null, rany, rcov, fail);
-        }
-        clock_end(AM_KERNEL_PRDC_VERIFY, st);
+    // budgets of the data-dependent fallback (cross_fast_decide_kernel).  The overflow queue's budget is enforced INSIDE
+    // the filter pass: entries past it raise the fail flag at once and the workgroups not yet started return at their
+    // first instruction - on inputs the bound cannot decide most of the pass's time went into those entries
+    // (an overflow-queue entry costs ~20 ns in its one-pair-per-thread kernel, a pair of the exact kernel 2 D / 140 TF:
+    // the budget is what costs a quarter of the exact kernel's time)
+    const long long pairs = (long long)Nr * (long long)Nc;
+    const long long limit_total = std::max<long long>(pairs / 128, 65536);
+    const int limit_overflow = (int)std::min<long long>(std::max<long long>((pairs >> 22) * D, 65536), p.ovcap);
+    clock_begin(AM_KERNEL_PRDC_CROSS, st);
+    // rows of up to 512 f16: the operand-stationary engine (pstat_engine.h), wider ones: both operands through LDS
+    const auto launch_main = wide_stationary(Dh) ? &launch_cross_pstat : &launch_cross_wide;
+    if ((rc = launch_main(want_min, (unsigned)p.blocks, Rb, Nr, ldb / 2, rn, rt, Cb, Nc, ldb / 2, cn, ct, Dh, p.nchunks, p.grp_rows,
+                          b.maxn, b.rmin_approx, rany, rcov, col_count, b.wgq, p.qcap, b.wgq_count, b.items, b.ovq, b.ov_count,
+                          limit_overflow, fail, fc, st)) != AM_OK)
+        return rc;
+    clock_end(AM_KERNEL_PRDC_CROSS, st);
+    hipLaunchKernelGGL(cross_fast_decide_kernel, dim3(1), dim3(64), 0, st, b.ov_count, p.ovcap, fail, limit_total, limit_overflow);
+    clock_begin(AM_KERNEL_PRDC_VERIFY, st);
+    if (h64 != nullptr) {
+        hipLaunchKernelGGL(cross_verify_regions64_kernel, dim3(CROSS_VERIFY_GRID), dim3(256), 0, st, *h64, D, b.wgq, p.qcap, b.wgq_count,
+                           b.items, b.ov_count + 2, col_count, rany, rcov, fail);
     } else {
-        clock_begin(AM_KERNEL_PRDC_CROSS, st);
-        if (want_min) launch_filter(&cross_fast_kernel<false, true>, (unsigned)p.blocks, p.nchunks, 1, p.grp_rows);
-        else launch_filter(&cross_fast_kernel<false, false>, (unsigned)p.blocks, p.nchunks, 1, p.grp_rows);
-        clock_end(AM_KERNEL_PRDC_CROSS, st);
-        AM_LAUNCH_CHECK();
-        const size_t verify_lds = (size_t)(4 * ((D + 7) / 8 * 8) + p.qcap) * sizeof(float);
-        clock_begin(AM_KERNEL_PRDC_VERIFY, st);
-        hipLaunchKernelGGL(cross_verify_kernel, dim3((unsigned)p.blocks), dim3(256), verify_lds, st, R, Nr, ldr, rn, rt, C, ldc, cn,
-                           ct, D, p.nchunks, p.grp_rows, b.wgq, p.qcap, b.wgq_count, col_count, rmin_or_null, rany, rcov);
-        clock_end(AM_KERNEL_PRDC_VERIFY, st);
+        AM_HIP_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(&cross_verify_regions_kernel), (int)VERIFY_LDS_BYTES));
+        hipLaunchKernelGGL(cross_verify_regions_kernel, dim3(CROSS_VERIFY_GRID), dim3(256), VERIFY_LDS_BYTES, st, R, ldr, rn, rt, C, ldc,
+                           cn, ct, D, b.wgq, p.qcap, b.wgq_count, b.items, b.ov_count + 2, col_count, rmin_or_null, rany, rcov, fail);
     }
+    clock_end(AM_KERNEL_PRDC_VERIFY, st);
     AM_LAUNCH_CHECK();
     if (h64 != nullptr)
         hipLaunchKernelGGL(cross_verify_overflow64_kernel, dim3(1024), dim3(256), 0, st, *h64, D, b.ovq, b.ov_count, p.ovcap, fail, col_count,
@@ -1701,8 +1473,7 @@ static int run_knn_fast(const float* X, int64_t N, int64_t ld, int D, int k1, co
     unsigned* maxn = f.maxn;
     float* thr = b.thr;
     // data-dependent fallback to the exact general kernel (knn_fast_predict_kernel): the single-GPU form only
-    static const int gate_on = env_int("AM_KNN_FAST_GATE", 1);
-    int* gate = (gate_on != 0 && bounds_in == nullptr && out_lists == nullptr) ? f.gate : nullptr;
+    int* gate = (bounds_in == nullptr && out_lists == nullptr) ? f.gate : nullptr;
     const int* skip_sweep = gate;
     const int* skip_verify = gate != nullptr ? gate + 1 : nullptr;
     if (gate != nullptr) AM_HIP_TRY(hipMemsetAsync(gate, 0, 4 * sizeof(int), st));

@@ -1,6 +1,6 @@
 // The 256 x 256 f16 FILTER kernels of the PRDC path (wide_engine.h): the membership filter cross_wide_kernel and the
 // symmetric k-NN sweep knn_wide_kernel, with their launchers.  Algorithms, error bound and queue protocol are documented
-// in pairwise_fast.h, which holds the 128-row forms of the same filters and everything that runs around these kernels.
+// in pairwise_fast.h, which holds the 128-row form of the k-NN sweep and everything that runs around these kernels.
 #include "wide_kernels.h"
 
 namespace am {

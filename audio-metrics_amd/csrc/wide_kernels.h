@@ -2,8 +2,8 @@
 // written once over an ENGINE policy (which pipeline multiplies the tiles, what its lanes own):
 //   WideEng          wide_engine.h   both operands streamed through LDS, a wave owns 128 Q x 64 P rows   (pairwise_wide.hip)
 //   PstatEng<KSLABS> pstat_engine.h  P block stationary in registers, a wave owns 128 Q x 32 P rows      (pairwise_pstat.hip)
-// Algorithms, error bound and queue protocol are documented in pairwise_fast.h, which holds the 128-row forms of the same
-// filters and everything that runs around these kernels.
+// Algorithms, error bound and queue protocol are documented in pairwise_fast.h, which holds the 128-row form of the
+// k-NN sweep and everything that runs around these kernels.
 #pragma once
 #include "pairwise_common.h"
 #include "wide_engine.h"
@@ -53,7 +53,9 @@ struct CrossWideEpilogue {
         const int slot = atomicAdd(qn, 1);
         if (slot < qcap) {
             wgq[slot] = make_uint2((unsigned)i, jflag);
-        } else if (*reinterpret_cast<volatile int*>(fail) == 0) {   // (see CrossFastEpilogue::push)
+        } else if (*reinterpret_cast<volatile int*>(fail) == 0) {   // region full: spill to the global queue
+            // (once the fail flag is up nothing is counted any more: on inputs the bound cannot decide - e.g. sets three
+            // orders of magnitude apart - billions of pairs arrive here and would wrap the counter)
             const unsigned s2 = atomicAdd(reinterpret_cast<unsigned*>(ov_count), 1u);
             if (s2 < (unsigned)ovcap) ovq[s2] = make_uint2((unsigned)i, jflag);
             else *fail = 1;

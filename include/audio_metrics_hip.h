@@ -1139,14 +1139,15 @@ int am_evaluate_sharded_f32(const float* ref_local, int64_t ld_ref, const float*
  * `rocprofv3 --kernel-trace --stats` prints for it) rather than of the whole entry point.
  *   AM_KERNEL_KNN          the k-NN tile kernel: knn_wide_kernel / knn_fast_kernel (f16 filter sweep) where the filter path runs,
  *                          else knn_sym_kernel, else knn_partial_kernel's main pass (sampled pre-passes not counted)
- *   AM_KERNEL_PRDC_CROSS   the membership tile kernel: cross_wide_kernel / cross_fast_kernel (f16 filter) or prdc_cross_kernel
+ *   AM_KERNEL_PRDC_CROSS   the membership tile kernel: cross_pstat*_kernel / cross_wide_kernel (f16 filter) or prdc_cross_kernel
  *   AM_KERNEL_KNN_VERIFY   knn_fast_verify_kernel (exact f32 values of the queued pairs)
- *   AM_KERNEL_PRDC_VERIFY  cross_verify_kernel
+ *   AM_KERNEL_PRDC_VERIFY  cross_verify_regions_kernel (cross_verify_regions64_kernel for float64 rows)
  * am_kernel_clock_read waits for the recorded launches, returns their count and summed duration in
  * milliseconds, and resets that kernel's record.  Disabled by default; no cost when disabled.
  * am_knn_path / am_prdc_path tell which form the library picks for a shape (0 = exact general kernel,
- * 1 = exact symmetric kernel (k-NN only), 2 = f16 filter + exact verification on the 128 x 128 engine,
- * 3 = the same on the 256 x 256 f16 engine, 4 = row-at-a-time kernel for k > AM_MAX_K).  The choice is a pure function of
+ * 1 = exact symmetric kernel (k-NN only), 2 = f16 filter + exact verification on the 128 x 128 engine (k-NN only),
+ * 3 = the same on the 256 x 256 f16 engine, 4 = row-at-a-time kernel for k > AM_MAX_K); am_prdc_path returns 0 or 3.
+ * The choice is a pure function of
  * the shapes; inside forms 2 / 3 the DATA can still hand a call to the exact kernels on the device (rows the f16 values
  * cannot separate, queue overflow, operands that cannot be scaled into f16) - am_filter_stats_enable counts those. */
 enum am_clocked_kernel { AM_KERNEL_KNN = 0, AM_KERNEL_PRDC_CROSS = 1, AM_KERNEL_KNN_VERIFY = 2, AM_KERNEL_PRDC_VERIFY = 3 };
