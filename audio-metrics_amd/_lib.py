@@ -108,6 +108,9 @@ SIGNATURES = {
     "am_fld_grad_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int]),
     "am_fld_grad_f32": (c_int, [_P, c_int64, c_int64, _P, c_int64, c_int64, c_int, _P, _P, _P, _P, _P, c_int64, c_double, c_double,
                                 _P, _P, _P, _P, c_size_t, _P]),
+    "am_logit_pass_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
+    "am_logit_pass_f32": (c_int, [_P, c_int64, c_int64, c_int, _P, c_int, _P, c_int, _P, _P, _P, _P, c_size_t, _P]),
+    "am_logit_pass_f64": (c_int, [_P, c_int64, c_int64, c_int, _P, c_int, _P, c_int, _P, _P, _P, _P, c_size_t, _P]),
     "am_sample_scores_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int]),
     "am_sample_scores_chunks": (c_int, [c_int64, c_int64, c_int]),
     "am_sample_scores_f32": (c_int, [_P, c_int64, c_int64, _P, c_int64, c_int64, c_int, _P, _P, _P, _P, _P, _P, _P, c_size_t,

@@ -520,6 +520,42 @@ def frechet_influence(rows, mu, b, lin, c0):
     return psi, sums
 
 
+LOGIT_MAX_MODELS = 16
+
+
+def logit_pass(rows, fold, label, coef, want_z=True):
+    """One fused pass of K linear logistic probes over the rows of ONE class (am_logit_pass_f32 / _f64, by the dtype of rows;
+    all arithmetic in f64, the same bits for float32 rows and their float64 copies).  fold: int32 device [N] (-1: the row
+    takes no part, 0..K-1: held out of that model, K: trains every model); label: 1 or 0, the class of every row; coef:
+    f64 device [K, D + 1], the weights in ROW coordinates and then the intercept.  Returns (sums f64 [K, D + 2] = {sum r x,
+    sum r, sum loss} over each model's training rows, z f64 [N] - the logit of every row under the model of its own fold,
+    NaN where it has none - or None with want_z=False, counts f64 [2] = {rows that took part, rows with a non-finite
+    element}), all on the device, stream-ordered, nothing waits for the device.  Two calls return the same bits."""
+    lib = _lib.load()
+    rows = as_rows(rows, "rows")
+    f64 = is_f64(rows)
+    n, d = rows.shape
+    coef = _f64(coef, "coef")
+    _require_cuda(fold, "fold")
+    if label not in (0, 1):
+        raise ValueError(f"label={label!r} must be 1 or 0 (the class of every row)")
+    if coef.dim() != 2 or coef.shape[1] != d + 1 or not 1 <= coef.shape[0] <= LOGIT_MAX_MODELS:
+        raise ValueError(f"coef must be [K, D + 1] with 1 <= K <= {LOGIT_MAX_MODELS} and D = {d}, got shape {tuple(coef.shape)}")
+    if n < 1 or fold.dim() != 1 or fold.shape[0] != n or fold.dtype != torch.int32:
+        raise ValueError(f"fold must be an int32 tensor with one entry per row ({n}), got {fold.dtype} {tuple(fold.shape)}")
+    fold = fold.contiguous()
+    dev = _same_device(rows, fold, coef)
+    k = coef.shape[0]
+    sums = torch.empty((k, d + 2), dtype=torch.float64, device=dev)
+    z = torch.empty(n, dtype=torch.float64, device=dev) if want_z else None
+    counts = torch.empty(2, dtype=torch.float64, device=dev)
+    nb = lib.am_logit_pass_workspace_bytes(n, d, k)
+    ws = _workspace(nb, dev)
+    _call(lib, "am_logit_pass_f64" if f64 else "am_logit_pass_f32", dev, _ptr(rows), n, _ld64(rows) if f64 else _ld(rows), d, _ptr(fold),
+          int(label), _ptr(coef), k, _ptr(sums), _ptr(z) if want_z else ctypes.c_void_p(None), _ptr(counts), _ptr(ws), nb)
+    return sums, z, counts
+
+
 FRECHET_BATCH_WS_CAP = 1 << 30     # bytes of solver workspace per library call; larger batches go in chunks of sets
 
 

@@ -713,6 +713,42 @@ int am_fld_grad_f32(const float* G, int64_t M, int64_t ldg, const float* X, int6
                     void* ws, size_t ws_bytes, am_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * LOGISTIC PROBES over the stored rows of one set (csrc/logit.hip)                    no counterpart in the reference
+ *   The fused pass of the classifier two-sample test: K linear models evaluated on every row of X, all rows of ONE class.
+ *     fold    DEVICE int32[N]: -1 = the row takes no part, 0..K-1 = held out of that model (it trains the other K - 1),
+ *             K = trains every model; any other value counts as -1
+ *     label   HOST: 1 or 0, the class of every row of X; s = +1 for 1, -1 for 0
+ *     coef    DEVICE double[K][D + 1]: a_k[0..D-1] in ROW coordinates, then the intercept b_k
+ *   Per row i and model k, all in f64 (float32 rows are converted on load, which is exact, so am_logit_pass_f32 returns the
+ *   SAME BITS as am_logit_pass_f64 on the same values):
+ *     z_ik = b_k + sum_d a_kd x_id  (the products summed first, in ascending groups of four columns on
+ *            v_mfma_f64_16x16x4_f64, b_k added last),   t = s z,
+ *     loss = max(-t, 0) + log1p(exp(-|t|)),   r = -s / (1 + exp(t))      (= p - y)
+ *   Outputs, all overwritten:
+ *     sums    DEVICE double[K][D + 2]: sum r x_d (d = 0..D-1), sum r, sum loss, over the rows that TRAIN model k - fold in
+ *             0..K, fold != k, every element finite
+ *     z_out   DEVICE double[N] or NULL: z under the model of the row's own fold; NaN for fold -1, fold K and for a row with
+ *             a non-finite element
+ *     counts  DEVICE double[2]: rows that took part (fold in 0..K, every element finite), rows with a non-finite element
+ *             (whatever their fold)
+ *   The kernel takes no weights: within one call the class weight is a constant the caller applies to the sums.
+ *   One workgroup owns 64 rows at a time and takes the row blocks g, g + grid, ... in order, grid = min(ceil(N / 64), 256) -
+ *   a function of N alone; its partial sums are written once and a second kernel adds the partials in workgroup order.  No
+ *   floating-point atomics: two calls return the same bits.  A model's sums and a row's z do not depend on the other models
+ *   of the call or on K, and z_out[i] depends on row i and its model alone - not on N, ld or the row's place in a tile.
+ *   Limits: N >= 1, 1 <= D <= 8192, 1 <= K <= 16, ld >= D; float32 rows 16-byte aligned with ld % 4 == 0 (AM_ERR_BAD_SHAPE);
+ *   a null pointer other than z_out or a label other than 0 / 1 is AM_ERR_BAD_ARG.  Workspace: [grid][K (D + 2) + 2]
+ *   doubles.  Everything is validated before the first HIP call; the call is asynchronous and reads nothing back.
+ * ------------------------------------------------------------------------- */
+size_t am_logit_pass_workspace_bytes(int64_t N, int D, int K);
+int am_logit_pass_f32(const float* X, int64_t N, int64_t ld, int D, const int32_t* fold, int label,
+                      const double* coef, int K, double* sums, double* z_out, double* counts,
+                      void* ws, size_t ws_bytes, am_stream_t stream);
+int am_logit_pass_f64(const double* X, int64_t N, int64_t ld, int D, const int32_t* fold, int label,
+                      const double* coef, int K, double* sums, double* z_out, double* counts,
+                      void* ws, size_t ws_bytes, am_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * PER-SAMPLE realism, ball count and rarity on the PRDC manifold (csrc/sample_scores.hip)   no counterpart in the reference
  *   X: the samples (N rows), Y: the manifold set (M rows), r_y: device float[M], the k-NN radius of row j of Y (what
  *   am_knn_radii_f32(Y, Y) returns).  One Gram pass on the exact f32 tile engine, no N x M matrix.  Per pair, all in f32:
