@@ -37,6 +37,7 @@ from .metrics.fkea import (vendi_score_rff, rke_score, kernel_novelty_score, rff
 from .metrics.fld import (feature_likelihood_divergence, feature_likelihood_fit, fld_adam_step,   # noqa: F401
                           fld_from_logliks, authenticity_score)
 from .metrics.c2st import classifier_two_sample_test, c2st_folds, c2st_summary, logistic_lbfgs   # noqa: F401
+from .metrics.nn_test import nearest_neighbor_two_sample_test, nn_permutation_null   # noqa: F401
 
 from .embed import ItemCategory, embedding_pipeline                            # noqa: F401
 from .projection import IncrementalPCA                                         # noqa: F401

@@ -98,6 +98,9 @@ SIGNATURES = {
     "am_knn_search_chunks": (c_int, [c_int64, c_int64, c_int, c_int]),
     "am_knn_search_f32": (c_int, [_P, c_int64, c_int64, _P, c_int64, c_int64, c_int, c_int, c_int64, c_int, _P, _P, _P, c_size_t,
                                   _P]),
+    "am_knn_search_groups_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int, c_int]),
+    "am_knn_search_groups_f32": (c_int, [_P, c_int64, c_int64, _P, _P, c_int64, c_int64, _P, c_int, c_int, c_int, _P, _P, _P, c_size_t,
+                                         _P]),
     "am_kmeans_assign_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int]),
     "am_kmeans_assign_f32": (c_int, [_P, c_int64, c_int64, _P, c_int64, c_int64, c_int, _P, _P, _P, _P, c_size_t, _P]),
     "am_softmin_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int]),

@@ -34,30 +34,12 @@
 //     KCAP 16:  64 list registers, __launch_bounds__(256, 2), two workgroups per CU
 //     KCAP 32: 128 list registers, __launch_bounds__(256, 1): ONE workgroup per CU (the lists alone are half of the 256
 //              registers a wave has at two per SIMD)
-#include "row_sweep.h"
+#include "knn_keys.h"
 
 namespace am {
 namespace search {
 
-constexpr int MAX_K = 32;
-constexpr unsigned long long EMPTY_KEY = 0x7f800000ffffffffull;          // (+inf, no column): larger than every real key
-constexpr unsigned INF_BITS = 0x7f800000u;
 constexpr size_t LDS_BYTES = (ENGINE_LDS_FLOATS + 2 * TB) * sizeof(float);   // staging slabs + [2][128] column norms
-
-__host__ __device__ constexpr int kcap_for(int k) { return k <= 8 ? 8 : k <= 16 ? 16 : 32; }
-
-// Branch-free sorted insertion of a key into an ascending list of CAP keys (list_insert of tile_engine.h on uint64:
-// compare-exchange down the list, fully unrolled).  A key >= best[CAP-1] falls through.
-template <int CAP>
-__device__ __forceinline__ void key_insert(unsigned long long (&best)[CAP], unsigned long long x) {
-#pragma unroll
-    for (int i = 0; i < CAP; ++i) {
-        const bool lt = x < best[i];
-        const unsigned long long lo = lt ? x : best[i];
-        x = lt ? best[i] : x;
-        best[i] = lo;
-    }
-}
 
 template <int KCAP>
 struct KnnIndexEpilogue {
@@ -222,16 +204,23 @@ __global__ void __launch_bounds__(256) knn_search_merge_kernel(const unsigned lo
     }
 }
 
-static bool shape_ok(int64_t N, int64_t M, int D, int k) { return k >= 1 && k <= MAX_K && sweep_shape_ok(N, M, D, COLUMNS_KEYED); }
+template <int KCAP>
+static int run_merge(const unsigned long long* partial, int64_t N, int nchunks, int k, int squared, float* out_dist, int64_t* out_idx,
+                     hipStream_t st) {
+    hipLaunchKernelGGL(knn_search_merge_kernel<KCAP>, dim3((unsigned)ceil_div(N, 256)), dim3(256), 0, st, partial, N, nchunks, k,
+                       squared, out_dist, out_idx);
+    AM_LAUNCH_CHECK();
+    return AM_OK;
+}
 
-struct Buffers {
-    float *xn, *yn;
-    unsigned long long* partial;
-};
-static void carve(Carver& c, int64_t N, int64_t M, int k, int nchunks, Buffers& b) {
-    b.xn = c.take<float>((size_t)N);
-    b.yn = c.take<float>((size_t)M);
-    b.partial = c.take<unsigned long long>((size_t)nchunks * (size_t)N * kcap_for(k));
+// (knn_keys.h: the grouped search of knn_groups.hip merges its partial lists with the same kernel)
+int launch_merge(int kcap, const unsigned long long* partial, int64_t N, int nchunks, int k, int squared, float* out_dist,
+                 int64_t* out_idx, hipStream_t st) {
+    switch (kcap) {
+        case 8:  return run_merge<8>(partial, N, nchunks, k, squared, out_dist, out_idx, st);
+        case 16: return run_merge<16>(partial, N, nchunks, k, squared, out_dist, out_idx, st);
+        default: return run_merge<32>(partial, N, nchunks, k, squared, out_dist, out_idx, st);
+    }
 }
 
 template <int KCAP>
@@ -241,10 +230,7 @@ static int run(const float* X, int64_t N, int64_t ldx, const float* xn, const fl
     const int rc = launch_sweep(&knn_search_kernel<KCAP, false>, &knn_search_kernel<KCAP, true>, LDS_BYTES, N, nchunks, D, st, X, N, ldx,
                                 xn, Y, M, ldy, yn, D, nchunks, self_offset, partial);
     if (rc != AM_OK) return rc;
-    hipLaunchKernelGGL(knn_search_merge_kernel<KCAP>, dim3((unsigned)ceil_div(N, 256)), dim3(256), 0, st, partial, N, nchunks, k,
-                       squared, out_dist, out_idx);
-    AM_LAUNCH_CHECK();
-    return AM_OK;
+    return run_merge<KCAP>(partial, N, nchunks, k, squared, out_dist, out_idx, st);
 }
 
 }  // namespace search

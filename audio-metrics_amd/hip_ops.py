@@ -1258,6 +1258,48 @@ def knn_search(x, y, k, self_offset=None, squared=False):
     return dist, idx
 
 
+def knn_search_groups(x, y, k, x_group, y_group, squared=False):
+    """The k nearest rows of y WITH ANOTHER LABEL for every row of x (am_knn_search_groups_f32): row j of y is skipped for
+    row i of x iff x_group[i] == y_group[j] - int32 device vectors, one label per row, any values.  Everything else is
+    knn_search: (dist float32 [N, k] ascending, idx int64 [N, k]) as device tensors, stream-ordered, nothing waits for the
+    device; the bits of knn_search's distances; ties go to the smallest row index of y; (+inf, -1) where a row has fewer
+    than k admissible finite candidates.  A set searched against itself with its own labels leaves out each row's whole
+    group, the row included."""
+    if is_f64(x) or is_f64(y):
+        raise NotImplementedError("knn_search_groups takes float32 rows (the float64 matrix-core form is not implemented)")
+    k = int(k)
+    if not 1 <= k <= KNN_SEARCH_MAX_K:
+        raise ValueError(f"k={k} must be in 1 .. {KNN_SEARCH_MAX_K}")
+    if x.dim() != 2 or y.dim() != 2:
+        raise ValueError(f"x and y must be 2-D, got shapes {tuple(x.shape)} and {tuple(y.shape)}")
+    if x.shape[1] != y.shape[1]:
+        raise ValueError(f"feature widths differ: {x.shape[1]} and {y.shape[1]}")
+    if x.shape[0] < 1 or y.shape[0] < 1:
+        raise ValueError(f"knn_search_groups needs rows on both sides (got {x.shape[0]} and {y.shape[0]})")
+    for labels, rows, name in ((x_group, x, "x_group"), (y_group, y, "y_group")):
+        if not torch.is_tensor(labels) or labels.dtype != torch.int32:
+            raise ValueError(f"{name} must be an int32 tensor, got {getattr(labels, 'dtype', type(labels).__name__)}")
+        if labels.dim() != 1 or labels.shape[0] != rows.shape[0]:
+            raise ValueError(f"{name} must hold one label per row: shape {tuple(labels.shape)} for {rows.shape[0]} rows")
+        if labels.device != rows.device:
+            raise ValueError(f"{name} lives on {labels.device}, its rows on {rows.device}")
+    lib = _lib.load()
+    same = x is y
+    x = as_matrix(x, "x")
+    y = x if same else as_matrix(y, "y")
+    dev = _same_device(x, y)
+    x_group, y_group = x_group.contiguous(), y_group.contiguous()
+    n, d = x.shape
+    m = y.shape[0]
+    dist = torch.empty((n, k), dtype=torch.float32, device=dev)
+    idx = torch.empty((n, k), dtype=torch.int64, device=dev)
+    nb = lib.am_knn_search_groups_workspace_bytes(n, m, d, k)
+    ws = _workspace(nb, dev)
+    _call(lib, "am_knn_search_groups_f32", dev, _ptr(x), n, _ld(x), _ptr(x_group), _ptr(y), m, _ld(y), _ptr(y_group), d, k,
+          1 if squared else 0, _ptr(dist), _ptr(idx), _ptr(ws), nb)
+    return dist, idx
+
+
 def knn_search_chunks(n, m, d, k):
     """Column chunks the search's plan cuts the rows of y into (am_knn_search_chunks; tests and tools)."""
     return int(_lib.load().am_knn_search_chunks(int(n), int(m), int(d), int(k)))

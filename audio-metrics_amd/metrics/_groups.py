@@ -46,3 +46,11 @@ def sort_into_groups(labels):
     uniq, counts = torch.unique_consecutive(sorted_labels, return_counts=True)
     host = torch.stack([uniq, counts]).cpu().numpy()
     return order, counts, host[0].copy(), host[1].astype(np.int64)
+
+
+def joint_group_ids(labels_x, labels_y, device):
+    """Dense int32 ids of two label vectors ON `device`, mapped JOINTLY so that equal labels of the two sets get equal
+    ids (hip_ops.knn_search_groups compares ids across the sets): one torch.unique over both, no read-back."""
+    both = torch.cat([labels_x.to(device=device, dtype=torch.int64), labels_y.to(device=device, dtype=torch.int64)])
+    inverse = torch.unique(both, return_inverse=True)[1].to(torch.int32)
+    return inverse[:labels_x.numel()].contiguous(), inverse[labels_x.numel():].contiguous()

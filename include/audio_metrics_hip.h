@@ -608,6 +608,27 @@ int am_knn_search_f32(const float* X, int64_t N, int64_t ldx, const float* Y, in
                       void* ws, size_t ws_bytes, am_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * k-nearest-neighbour search that LEAVES A GROUP OUT (csrc/knn_groups.hip)       no counterpart in the reference
+ *   Every row of X and of Y carries one int32 label (the song a window was cut from).  For every row i of X the k nearest
+ *   rows of Y whose label DIFFERS from x_group[i]: column j is skipped for row i iff x_group[i] == y_group[j], for any
+ *   int32 values (labels are moved and compared for equality, never computed with).  There is no self offset: a set
+ *   searched against itself with its own labels excludes each row through its own group.
+ *   Everything else is am_knn_search_f32: the arithmetic of a pair and the bits of every distance, squared, the order
+ *   (ties to the SMALLEST row index of Y, independent of chunking: two calls return the same bits), the chunk plan
+ *   (am_knn_search_chunks), the partial lists and the merge kernel, (+inf, -1) where a row has fewer than k admissible
+ *   finite candidates; a row with a non-finite element has no neighbours and is nobody's neighbour.
+ *   x_group, y_group: device pointers, N and M values; null -> AM_ERR_BAD_ARG.  1 <= k <= 32 (else AM_ERR_BAD_SHAPE);
+ *   M < 2^32 - 1; X, Y as for am_knn_search_f32.  Workspace (caller-owned; the library allocates nothing): the row norms
+ *   and uint64 [am_knn_search_chunks][N][8 / 16 / 32] partial lists.  Everything is validated before the first HIP call;
+ *   the call is asynchronous.
+ * ------------------------------------------------------------------------- */
+size_t am_knn_search_groups_workspace_bytes(int64_t N, int64_t M, int D, int k);
+int am_knn_search_groups_f32(const float* X, int64_t N, int64_t ldx, const int32_t* x_group,
+                             const float* Y, int64_t M, int64_t ldy, const int32_t* y_group,
+                             int D, int k, int squared, float* out_dist, int64_t* out_idx,
+                             void* ws, size_t ws_bytes, am_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * K-MEANS, the two halves of a Lloyd iteration (csrc/kmeans.hip)              no counterpart in the reference
  *   Every pointer below is a DEVICE pointer, `inertia` included: an iteration needs no read-back.  Everything is validated
  *   before the first HIP call; the calls are asynchronous.  No floating-point atomics: two calls return the same bits.
