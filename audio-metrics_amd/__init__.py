@@ -23,6 +23,7 @@ from .metrics.mmd import kernel_audio_distance_multiscale, energy_distance   # n
 from .metrics.prdc import prdc, nearest_neighbour_distances                   # noqa: F401
 from .metrics.neighbors import nearest_neighbors                              # noqa: F401
 from .metrics.fidelity import sample_fidelity, sample_fidelity_per_group, fidelity_by_group   # noqa: F401
+from .metrics.prdc_groups import leave_group_out_radii, prdc_leave_group_out    # noqa: F401
 from .metrics.pprecall import probabilistic_precision_recall, probabilistic_precision_per_group   # noqa: F401
 from .metrics.pprecall import psr_radius, psr_by_group                        # noqa: F401
 from .metrics.mauve import kmeans, mauve_score, mauve_from_histograms         # noqa: F401

@@ -41,18 +41,15 @@
 //
 // Register budget: 64 accumulators, 64 staging registers, 32 fragment registers, 8 key registers and 2 counts;
 // __launch_bounds__(256, 2), two workgroups per CU (2 x 75 KiB of LDS), no scratch (tests/test_sample_scores_resources_cpu.py).
-#include "row_sweep.h"
+//
+// The keys, the gate's constants, the workspace layout and the launchers of the two small kernels are in
+// sample_scores_keys.h: sample_scores_groups.hip (a pair of equal labels is no pair) shares them.
+#include "sample_scores_keys.h"
 
 namespace am {
 namespace scores {
 
-constexpr unsigned long long NO_MEMBER = 0xffffffffffffffffull;          // min key of a row outside every ball
 constexpr size_t LDS_BYTES = (ENGINE_LDS_FLOATS + 2 * 3 * TB) * sizeof(float);   // staging slabs + [2][3][128] column values
-constexpr int MERGE_THREADS = 256;
-constexpr float GATE_SHRINK = 1.f - 9.5367431640625e-07f;                // 1 - 2^-20
-constexpr float GATE_TINY = 7.888609052210118e-31f;                      // 2^-100
-constexpr float F32_MAX = 3.4028234663852886e+38f;
-constexpr float F32_MIN_NORMAL = 1.1754943508222875e-38f;
 
 // cleaned radius (0 for one that is not > 0) and the threshold the tile kernel compares the unclamped d2 with
 __global__ void scores_columns_kernel(const float* __restrict__ r_y, int64_t M, float* __restrict__ rad, float* __restrict__ thr) {
@@ -251,21 +248,19 @@ sample_scores_merge_kernel(const unsigned long long* __restrict__ pmax, const un
     out_rarity_idx[i] = member ? (int64_t)(unsigned)lo : (int64_t)-1;
 }
 
-static bool shape_ok(int64_t N, int64_t M, int D) { return sweep_shape_ok(N, M, D, COLUMNS_KEYED); }
+int launch_columns(const float* r_y, int64_t M, float* rad, float* thr, hipStream_t st) {
+    hipLaunchKernelGGL(scores_columns_kernel, dim3((unsigned)ceil_div(M, 256)), dim3(256), 0, st, r_y, M, rad, thr);
+    AM_LAUNCH_CHECK();
+    return AM_OK;
+}
 
-struct Buffers {
-    float *xn, *yn, *thr, *rad;
-    unsigned long long *pmax, *pmin;
-    int* pcnt;
-};
-static void carve(Carver& c, int64_t N, int64_t M, int nchunks, Buffers& b) {
-    b.xn = c.take<float>((size_t)N);
-    b.yn = c.take<float>((size_t)M);
-    b.thr = c.take<float>((size_t)M);
-    b.rad = c.take<float>((size_t)M);
-    b.pmax = c.take<unsigned long long>((size_t)nchunks * (size_t)N);
-    b.pmin = c.take<unsigned long long>((size_t)nchunks * (size_t)N);
-    b.pcnt = c.take<int>((size_t)nchunks * (size_t)N);
+int launch_merge(const unsigned long long* pmax, const unsigned long long* pmin, const int* pcnt, int64_t N, int nchunks,
+                 float* out_realism, int64_t* out_realism_idx, int32_t* out_count, float* out_rarity, int64_t* out_rarity_idx,
+                 hipStream_t st) {
+    hipLaunchKernelGGL(sample_scores_merge_kernel, dim3((unsigned)ceil_div(N, MERGE_THREADS)), dim3(MERGE_THREADS), 0, st, pmax, pmin,
+                       pcnt, N, nchunks, out_realism, out_realism_idx, out_count, out_rarity, out_rarity_idx);
+    AM_LAUNCH_CHECK();
+    return AM_OK;
 }
 
 }  // namespace scores
@@ -307,14 +302,10 @@ extern "C" int am_sample_scores_f32(const float* X, int64_t N, int64_t ldx, cons
     hipStream_t st = static_cast<hipStream_t>(stream);
     const float* yn;
     if ((rc = launch_norms_pair(X, N, ldx, Y, M, ldy, D, b.xn, b.yn, st, &yn)) != AM_OK) return rc;
-    hipLaunchKernelGGL(scores::scores_columns_kernel, dim3((unsigned)ceil_div(M, 256)), dim3(256), 0, st, r_y, M, b.rad, b.thr);
-    AM_LAUNCH_CHECK();
+    if ((rc = scores::launch_columns(r_y, M, b.rad, b.thr, st)) != AM_OK) return rc;
     rc = launch_sweep(&scores::sample_scores_kernel<false>, &scores::sample_scores_kernel<true>, scores::LDS_BYTES, N, nchunks, D, st, X,
                       N, ldx, b.xn, Y, M, ldy, yn, b.thr, b.rad, D, nchunks, b.pmax, b.pmin, b.pcnt);
     if (rc != AM_OK) return rc;
-    hipLaunchKernelGGL(scores::sample_scores_merge_kernel, dim3((unsigned)ceil_div(N, scores::MERGE_THREADS)),
-                       dim3(scores::MERGE_THREADS), 0, st, (const unsigned long long*)b.pmax, (const unsigned long long*)b.pmin,
-                       (const int*)b.pcnt, N, nchunks, out_realism, out_realism_idx, out_count, out_rarity, out_rarity_idx);
-    AM_LAUNCH_CHECK();
-    return AM_OK;
+    return scores::launch_merge(b.pmax, b.pmin, b.pcnt, N, nchunks, out_realism, out_realism_idx, out_count, out_rarity, out_rarity_idx,
+                                st);
 }

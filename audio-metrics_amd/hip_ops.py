@@ -1351,6 +1351,55 @@ def sample_scores_chunks(n, m, d):
     return int(_lib.load().am_sample_scores_chunks(int(n), int(m), int(d)))
 
 
+def sample_scores_groups(x, y, r_y, x_group, y_group):
+    """sample_scores over the pairs of DIFFERENT labels (am_sample_scores_groups_f32): row j of y is no reference row of
+    row i of x iff x_group[i] == y_group[j] - int32 device vectors, one label per row, any values - so it is not counted,
+    its ratio is 0 and it is no candidate of the rarity.  Everything else is sample_scores: the same five device tensors
+    (realism float32 [N], realism_index int64 [N], ball_count int32 [N], rarity float32 [N], rarity_index int64 [N]),
+    stream-ordered, nothing waits for the device; the bits of sample_scores on the admissible columns; ties go to the
+    smallest row index of y; (0, -1, 0, 0.0, -1) for a row with no admissible reference row.  A set scored against itself
+    with its own labels scores every row against the other groups."""
+    if is_f64(x) or is_f64(y) or is_f64(r_y):
+        raise NotImplementedError("sample_scores_groups takes float32 rows (the float64 matrix-core form is not implemented)")
+    if x.dim() != 2 or y.dim() != 2:
+        raise ValueError(f"x and y must be 2-D, got shapes {tuple(x.shape)} and {tuple(y.shape)}")
+    if x.shape[1] != y.shape[1]:
+        raise ValueError(f"feature widths differ: {x.shape[1]} and {y.shape[1]}")
+    if x.shape[0] < 1 or y.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError(f"sample_scores_groups needs rows on both sides (got shapes {tuple(x.shape)} and {tuple(y.shape)})")
+    if not torch.is_tensor(r_y) or r_y.dim() != 1 or r_y.shape[0] != y.shape[0] or r_y.dtype != torch.float32:
+        raise ValueError(f"r_y must be a float32 tensor with one radius per row of y ({y.shape[0]}), got "
+                         f"{tuple(r_y.shape) if torch.is_tensor(r_y) else type(r_y).__name__}"
+                         f"{' ' + str(r_y.dtype) if torch.is_tensor(r_y) else ''}")
+    for labels, rows, name in ((x_group, x, "x_group"), (y_group, y, "y_group")):
+        if not torch.is_tensor(labels) or labels.dtype != torch.int32:
+            raise ValueError(f"{name} must be an int32 tensor, got {getattr(labels, 'dtype', type(labels).__name__)}")
+        if labels.dim() != 1 or labels.shape[0] != rows.shape[0]:
+            raise ValueError(f"{name} must hold one label per row: shape {tuple(labels.shape)} for {rows.shape[0]} rows")
+        if labels.device != rows.device:
+            raise ValueError(f"{name} lives on {labels.device}, its rows on {rows.device}")
+    lib = _lib.load()
+    same = x is y
+    x = as_matrix(x, "x")
+    y = x if same else as_matrix(y, "y")
+    _require_cuda(r_y, "r_y")
+    dev = _same_device(x, y, r_y)
+    r_y = r_y.contiguous()
+    x_group, y_group = x_group.contiguous(), y_group.contiguous()
+    n, d = x.shape
+    m = y.shape[0]
+    realism = torch.empty(n, dtype=torch.float32, device=dev)
+    realism_idx = torch.empty(n, dtype=torch.int64, device=dev)
+    count = torch.empty(n, dtype=torch.int32, device=dev)
+    rarity = torch.empty(n, dtype=torch.float32, device=dev)
+    rarity_idx = torch.empty(n, dtype=torch.int64, device=dev)
+    nb = lib.am_sample_scores_groups_workspace_bytes(n, m, d)
+    ws = _workspace(nb, dev)
+    _call(lib, "am_sample_scores_groups_f32", dev, _ptr(x), n, _ld(x), _ptr(x_group), _ptr(y), m, _ld(y), _ptr(y_group), d, _ptr(r_y),
+          _ptr(realism), _ptr(realism_idx), _ptr(count), _ptr(rarity), _ptr(rarity_idx), _ptr(ws), nb)
+    return realism, realism_idx, count, rarity, rarity_idx
+
+
 # ---- probabilistic scoring rule of a point against a set (csrc/psr.hip) ----
 PSR_RADIUS_SQ_MAX = 3.4028234663852886e+38                     # FLT_MAX: the in-range threshold is a float32
 

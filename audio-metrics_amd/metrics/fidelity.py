@@ -16,6 +16,7 @@ import torch
 
 from .. import hip_ops as ops
 from ._groups import labelled_rows
+from .prdc_groups import grouped_scores
 
 
 def _check_sets(function_name, samples, manifold, nearest_k, sample_rows=None):
@@ -39,11 +40,13 @@ def _check_sets(function_name, samples, manifold, nearest_k, sample_rows=None):
     return rows[0], rows[1], k
 
 
-def _scores_on_host(ex, manifold, ey, k, device_labels=None):
+def _scores_on_host(ex, manifold, ey, k, device_labels=None, scores=None):
     """The five per-row vectors as numpy, from ONE read-back: the float32 bit patterns and the int32 counts travel beside
-    the indices as int64 [n, 5] (labels that live on the device ride along as a sixth column, "labels")."""
-    radii = manifold.get_radii(k)
-    realism, realism_idx, count, rarity, rarity_idx = ops.sample_scores(ex, ey, radii)
+    the indices as int64 [n, 5] (labels that live on the device ride along as a sixth column, "labels").  `scores`: the
+    five device tensors where the caller has run the pass already (the leave-group-out forms)."""
+    if scores is None:
+        scores = ops.sample_scores(ex, ey, manifold.get_radii(k))
+    realism, realism_idx, count, rarity, rarity_idx = scores
     columns = [realism.view(torch.int32).to(torch.int64), realism_idx, count.to(torch.int64),
                rarity.view(torch.int32).to(torch.int64), rarity_idx]
     if device_labels is not None:
@@ -58,7 +61,7 @@ def _scores_on_host(ex, manifold, ey, k, device_labels=None):
             "rarity_index": both[:, 4].copy()}
 
 
-def sample_fidelity(samples, manifold, nearest_k=5):
+def sample_fidelity(samples, manifold, nearest_k=5, groups=None, manifold_groups=None, match_across_sets=True):
     """Realism, ball count and rarity of every stored row of `samples` on the k-NN manifold of `manifold`.  Returns numpy
     arrays in stored row order of samples, from one read-back:
       realism float32 [n], realism_index int64 [n] (the manifold row that attains it; ties to the smallest index; -1 where
@@ -66,9 +69,21 @@ def sample_fidelity(samples, manifold, nearest_k=5):
       ball_count int32 [n] (the balls the row lies in), in_manifold bool [n] (ball_count > 0),
       rarity float32 [n] and rarity_index int64 [n] (0.0 and -1 for a row outside every ball), nearest_k,
       precision = (#in_manifold) / n and density = (1 / k) * (sum(ball_count) / n), equal to prdc(manifold, samples, k)'s.
-    float32 rows.  `samples` may be `manifold`: nothing is skipped, so every row then has realism +inf."""
+    float32 rows.  `samples` may be `manifold`: nothing is skipped, so every row then has realism +inf.
+
+    groups / manifold_groups: one integer label per stored row of samples / of manifold (the song a window was cut from; any
+    integer dtype, host or device, any order; compared by VALUE across the two sets).  With manifold_groups the radii are
+    the leave-group-out radii of the manifold (metrics/prdc_groups.py: leave_group_out_radii; 1 <= nearest_k <= 32); with
+    groups as well and match_across_sets=True a manifold row of the sample's own label is no reference row of it
+    (ops.sample_scores_groups), and precision and density EQUAL prdc_leave_group_out's.  With `samples is manifold`
+    manifold_groups defaults to groups: every row is scored against the OTHER songs, the leave-one-out form.  Without the
+    two keywords this is the path above, unchanged."""
     ex, ey, k = _check_sets("sample_fidelity", samples, manifold, nearest_k)
-    out = _scores_on_host(ex, manifold, ex if samples is manifold else ey, k)
+    scores = None
+    if groups is not None or manifold_groups is not None:
+        scores = grouped_scores("sample_fidelity", samples, ex, manifold, ex if samples is manifold else ey, k, groups,
+                                manifold_groups, match_across_sets)
+    out = _scores_on_host(ex, manifold, ex if samples is manifold else ey, k, scores=scores)
     n = out["ball_count"].shape[0]
     out["in_manifold"] = out["ball_count"] > 0
     out["nearest_k"] = k
@@ -123,16 +138,24 @@ def fidelity_by_group(labels, realism, ball_count, rarity, nearest_k):
             "rarity_median_per_group": rarity_median}
 
 
-def sample_fidelity_per_group(samples, manifold, groups, nearest_k=5, return_rows=False):
+def sample_fidelity_per_group(samples, manifold, groups, nearest_k=5, return_rows=False, manifold_groups=None,
+                              match_across_sets=True):
     """sample_fidelity aggregated over row groups of `samples` (`groups`: one integer label per stored row, e.g. the song a
     clip was cut from): group_labels (ascending), group_sizes, precision_per_group, density_per_group,
     realism_median_per_group, rarity_median_per_group (over the group's in-manifold rows; NaN when it has none) and
     nearest_k; return_rows=True adds the per-row arrays of sample_fidelity.  One read-back; the aggregation runs on the host
-    over the vectors already read back (fidelity_by_group)."""
+    over the vectors already read back (fidelity_by_group).  manifold_groups (one label per stored row of manifold): the
+    leave-group-out form of sample_fidelity, with `groups` doubling as the labels of the samples; without it this is the
+    plain path, unchanged."""
     rows, n, labels = labelled_rows(samples, groups, "sample_fidelity_per_group", "its sample set")
     ex, ey, k = _check_sets("sample_fidelity_per_group", samples, manifold, nearest_k, sample_rows=rows)
+    scores = None
+    if manifold_groups is not None:
+        scores = grouped_scores("sample_fidelity_per_group", samples, ex, manifold, ex if samples is manifold else ey, k, groups,
+                                manifold_groups, match_across_sets)
     on_device = labels.device.type != "cpu"
-    per_row = _scores_on_host(ex, manifold, ex if samples is manifold else ey, k, device_labels=labels if on_device else None)
+    per_row = _scores_on_host(ex, manifold, ex if samples is manifold else ey, k, device_labels=labels if on_device else None,
+                              scores=scores)
     host_labels = per_row.pop("labels") if on_device else labels.numpy()
     out = fidelity_by_group(host_labels, per_row["realism"], per_row["ball_count"], per_row["rarity"], k)
     out["nearest_k"] = k

@@ -34,6 +34,7 @@ import numpy as np
 import torch
 
 from .. import hip_ops as ops
+from .prdc_groups import grouped_authenticity
 
 _ADAM_B1, _ADAM_B2, _ADAM_EPS = 0.9, 0.999, 1e-8
 
@@ -228,22 +229,31 @@ def feature_likelihood_divergence(gen, train, test, steps=100, lr=0.5, min_log_v
     return out
 
 
-def authenticity_score(gen, train, return_rows=False):
+def authenticity_score(gen, train, return_rows=False, train_groups=None, groups=None):
     """The share of generated rows that are not closer to a training row than that row's own nearest training neighbour
     (Alaa et al. 2022): row j of `gen` is authentic when |g_j - x_i| > |x_i - x_i'|, x_i the training row nearest to g_j
     (ops.knn_search(gen, train, 1)) and x_i' the training row nearest to x_i other than itself (train.get_radii(1): the second
     smallest distance of a row to its own set, a duplicate of the row counting as another row at distance 0).  The rows are
     taken as they are, float32 distances, a strict comparison; a generated row with no finite distance is not authentic.
     Returns {"authenticity": fraction}; return_rows=True adds "authentic" (numpy bool [M]) and "authenticity_nearest_train"
-    (int64 [M], -1 where there is none) in stored row order of gen.  One read-back."""
+    (int64 [M], -1 where there is none) in stored row order of gen.  One read-back.
+
+    train_groups / groups: one integer label per stored row of train / of gen (the song a window was cut from).  With
+    train_groups a training row's own-set neighbour distance is its distance to the nearest training row WITH ANOTHER LABEL
+    (metrics/prdc_groups.py: leave_group_out_radii(train, train_groups, 1)) - a sibling window of its own song is no
+    neighbour; with groups as well the nearest training row of a generated row is searched among the other labels, compared
+    by value (ops.knn_search_groups).  Without the two keywords this is the path above, unchanged."""
     g, x = _rows_of(gen, "generated", "authenticity_score"), _rows_of(train, "training", "authenticity_score")
     if g.shape[1] != x.shape[1]:
         raise ValueError(f"feature widths differ: {g.shape[1]} and {x.shape[1]}")
-    dist, idx = ops.knn_search(g, x, 1)
-    radii = train.get_radii(1)
-    found = idx[:, 0] >= 0
-    authentic = found & (dist[:, 0] > radii[idx[:, 0].clamp(min=0)])
+    if train_groups is not None or groups is not None:
+        dist0, idx0, radii = grouped_authenticity("authenticity_score", g, gen, x, train, train_groups, groups)
+    else:
+        dist, idx = ops.knn_search(g, x, 1)
+        dist0, idx0, radii = dist[:, 0], idx[:, 0], train.get_radii(1)
+    found = idx0 >= 0
+    authentic = found & (dist0 > radii[idx0.clamp(min=0)])
     if not return_rows:
         return {"authenticity": float(authentic.to(torch.float64).mean())}
-    host = torch.stack([authentic.to(torch.int64), idx[:, 0]]).cpu().numpy()
+    host = torch.stack([authentic.to(torch.int64), idx0]).cpu().numpy()
     return {"authenticity": float(host[0].mean()), "authentic": host[0].astype(bool), "authenticity_nearest_train": host[1].copy()}

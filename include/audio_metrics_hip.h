@@ -799,6 +799,34 @@ int am_sample_scores_f32(const float* X, int64_t N, int64_t ldx, const float* Y,
                          void* ws, size_t ws_bytes, am_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * PER-SAMPLE realism, ball count and rarity that LEAVE A GROUP OUT (csrc/sample_scores_groups.hip)   no counterpart in the reference
+ *   am_sample_scores_f32 with one int32 label per row of X and per row of Y (the song a window was cut from).  A pair
+ *   (i, j) with x_group[i] == y_group[j] is NO PAIR, for any int32 values (labels are moved and compared for equality,
+ *   never computed with): it is not counted, its ratio is 0, it is no candidate of the rarity.
+ *     out_realism[i]     = sqrt_rn(max { q_ij : y_group[j] != x_group[i] }), out_realism_idx[i] the j that attains it, ties to
+ *                          the SMALLEST j; 0.0f and -1 where the maximum is 0 (a non-finite sample row, no admissible row of
+ *                          Y with a positive radius at a finite distance, every row of Y in the row's own group)
+ *     out_count[i]       = #{ j : y_group[j] != x_group[i], member }
+ *     out_rarity[i]      = min { r_j : y_group[j] != x_group[i], member }, out_rarity_idx[i] the j that attains it, ties to
+ *                          the smallest j; 0.0f and -1 for a row outside every admissible ball
+ *   Everything else is am_sample_scores_f32, to the bit: d2, the cleaned radii, the strict membership test, the correctly
+ *   rounded ratio and its square root, the order of ties, the chunk plan (am_sample_scores_chunks), the partials and the
+ *   merge kernel.  With label values that no row of the other set carries the five outputs ARE those of
+ *   am_sample_scores_f32; with one value on every row of both sets every row gets (0, -1, 0, 0, -1).  X may be Y with
+ *   x_group == y_group: every row is then scored against the rows of the OTHER groups, itself excluded through its own.
+ *   No floating-point atomics: two calls return the same bits, whatever the chunking.
+ *   x_group, y_group: device pointers, N and M values; null -> AM_ERR_BAD_ARG.  M < 2^32 - 1; X, Y as for
+ *   am_knn_search_f32 (16-byte aligned, ld % 4 == 0, ld >= D).  Workspace (caller-owned; the library allocates nothing):
+ *   that of am_sample_scores_f32.  Everything is validated before the first HIP call; the call is asynchronous.
+ * ------------------------------------------------------------------------- */
+size_t am_sample_scores_groups_workspace_bytes(int64_t N, int64_t M, int D);
+int am_sample_scores_groups_f32(const float* X, int64_t N, int64_t ldx, const int32_t* x_group,
+                                const float* Y, int64_t M, int64_t ldy, const int32_t* y_group, int D,
+                                const float* r_y, float* out_realism, int64_t* out_realism_idx, int32_t* out_count,
+                                float* out_rarity, int64_t* out_rarity_idx,
+                                void* ws, size_t ws_bytes, am_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * PROBABILISTIC scoring rule of a point against a set (csrc/psr.hip)                  no counterpart in the reference
  *   The per-row quantity of probabilistic precision and recall (Park & Kim, ICCV 2023).  X: the points (N rows), Y: the
  *   set (M rows), radius: ONE radius for the whole set Y, a HOST double.  One Gram pass on the exact f32 tile engine, no
