@@ -39,6 +39,8 @@ from .metrics.fld import (feature_likelihood_divergence, feature_likelihood_fit,
                           fld_from_logliks, authenticity_score)
 from .metrics.c2st import classifier_two_sample_test, c2st_folds, c2st_summary, logistic_lbfgs   # noqa: F401
 from .metrics.nn_test import nearest_neighbor_two_sample_test, nn_permutation_null   # noqa: F401
+from .metrics.dependence import (distance_correlation, kernel_alignment, dependence_from_sums,   # noqa: F401
+                                 dependence_permutations, row_dependence, dcor_t_test)
 
 from .embed import ItemCategory, embedding_pipeline                            # noqa: F401
 from .projection import IncrementalPCA                                         # noqa: F401

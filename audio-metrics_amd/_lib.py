@@ -84,6 +84,9 @@ SIGNATURES = {
     "am_mmd_rbf_groups_workspace_bytes": (c_size_t, [c_int64, c_int, c_int64, c_int]),
     "am_mmd_rbf_groups_f32": (c_int, [_P, c_int64, c_int64, _P, _P, c_int, _P, c_int64, c_int64, c_int, _P, c_double, _P, _P, _P,
                                       c_size_t, _P]),
+    "am_pair_dependence_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
+    "am_pair_dependence_f32": (c_int, [_P, c_int64, c_int64, c_int, _P, c_int64, c_int, _P, c_int, _P, c_double, _P, c_double, _P, _P,
+                                       _P, c_size_t, _P]),
     "am_pairwise_select_f64_workspace_bytes": (c_size_t, [c_int64, c_int]),
     "am_pairwise_select_f64": (c_int, [_P, c_int64, c_int64, c_int, c_int64, _P, _P, c_size_t, _P]),
     "am_mmd_rbf_f64_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int, ctypes.c_uint]),

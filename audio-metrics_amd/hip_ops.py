@@ -1120,6 +1120,71 @@ def mmd_multi_sums(x, y, kernel, scales, bw2=None, blocks=7, out=None):
     return out
 
 
+PAIR_DEPENDENCE_MIN_ROWS = 4                                         # the unbiased statistics divide by n - 3
+
+
+def _side_bandwidth(kernel, bw2, name):
+    """(device pointer, host value) of one side's squared bandwidth for pair_dependence."""
+    if kernel == "energy":
+        return ctypes.c_void_p(None), 0.0
+    if bw2 is None:
+        raise ValueError(f'the "{kernel}" kernel needs {name} (a float32 device scalar or a number)')
+    if torch.is_tensor(bw2):
+        _require_cuda(bw2, name)
+        if bw2.dtype != torch.float32 or bw2.numel() != 1:
+            raise ValueError(f"{name} must be a float32 device scalar")
+        return _ptr(bw2), 0.0
+    host = float(bw2)
+    if not (host > 0.0 and host < float("inf")):
+        raise ValueError(f"{name}={bw2!r} must be finite and positive")
+    return ctypes.c_void_p(None), host
+
+
+def pair_dependence(x, y, kernel, bw2x=None, bw2y=None, perm=None):
+    """Row sums of the product of two Gram matrices of PAIRED sets in one library call (am_pair_dependence_f32): row i of x
+    [n, dx] belongs to row i of y [n, dy] - with `perm` (int64 device tensor [n]) to row perm[i] of y, addressed through the
+    list, no gathered copy.  Returns (rows, sums), float64 device tensors: rows [n, 5] = {A_i, B_i, H_i, AA_i, BB_i} with
+    A_i = sum_{j != i} a_ij, B_i = sum b_ij, H_i = sum a_ij b_ij, AA_i = sum a_ij^2, BB_i = sum b_ij^2, and sums [8] = their
+    five totals, sum A_i B_i, the number of finite rows and the number of non-finite rows (whose values are NaN).  `kernel`:
+    "energy" a = +|x_i - x_j| (distance covariance), "gaussian" exp(-d2 / (2 bw2)), "laplacian" exp(-d / sqrt(bw2)), with
+    `bw2x` / `bw2y` the squared bandwidth of each side: a 0-dim float32 DEVICE tensor (the output of pairwise_select_sq, no
+    host round trip) or a number.  float32 rows only; stream-ordered, nothing waits for the device."""
+    if kernel not in MMD_KERNELS:
+        raise ValueError(f"kernel={kernel!r} is not one of {sorted(MMD_KERNELS)}")
+    for t, name in ((x, "x"), (y, "y")):
+        if is_f64(t):
+            raise NotImplementedError(f"pair_dependence takes float32 rows ({name} holds float64 rows; the float64 matrix-core "
+                                      "form is not implemented)")
+        if not torch.is_tensor(t) or t.dim() != 2:
+            raise ValueError(f"{name} must be a 2-D tensor, got {tuple(getattr(t, 'shape', ()))}")
+    if x.shape[0] != y.shape[0]:
+        raise ValueError(f"row counts differ: {x.shape[0]} and {y.shape[0]} (row i of x belongs to row i of y)")
+    n = int(x.shape[0])
+    if n < PAIR_DEPENDENCE_MIN_ROWS:
+        raise ValueError(f"{n} paired rows: the unbiased statistics need at least {PAIR_DEPENDENCE_MIN_ROWS}")
+    if x.shape[1] < 1 or y.shape[1] < 1:
+        raise ValueError(f"feature widths {x.shape[1]} and {y.shape[1]} must be at least 1")
+    if perm is not None and (not torch.is_tensor(perm) or perm.dim() != 1 or perm.numel() != n or perm.dtype != torch.int64):
+        raise ValueError(f"perm must be an int64 tensor of the {n} row indices of y")
+    if x.device != y.device or (perm is not None and perm.device != x.device):
+        raise ValueError("x, y and perm must be on one device")
+    (bwx_arg, bwx_host), (bwy_arg, bwy_host) = _side_bandwidth(kernel, bw2x, "bw2x"), _side_bandwidth(kernel, bw2y, "bw2y")
+    lib = _lib.load()
+    x, y = as_matrix(x, "x"), as_matrix(y, "y")
+    dev = _same_device(x, y)
+    if perm is not None:
+        _require_cuda(perm, "perm")
+        perm = perm.contiguous()
+    rows = torch.empty((n, 5), dtype=torch.float64, device=dev)
+    sums = torch.empty(8, dtype=torch.float64, device=dev)
+    nb = lib.am_pair_dependence_workspace_bytes(n, x.shape[1], y.shape[1])
+    ws = _workspace(nb, dev)
+    _call(lib, "am_pair_dependence_f32", dev, _ptr(x), n, _ld(x), x.shape[1], _ptr(y), _ld(y), y.shape[1],
+          _ptr(perm) if perm is not None else ctypes.c_void_p(None), MMD_KERNELS[kernel], bwx_arg, bwx_host, bwy_arg, bwy_host,
+          _ptr(rows), _ptr(sums), _ptr(ws), nb)
+    return rows, sums
+
+
 def mmd_rbf_group_sums(x, idx, offsets, y, bw2=None, gamma=None, rows=False):
     """Per-group Gaussian kernel sums in one library call (am_mmd_rbf_groups_f32; both sets float64:
     am_mmd_rbf_groups_f64): group b is the rows

@@ -527,6 +527,39 @@ int am_mmd_rbf_groups_f32(const float* X, int64_t N1, int64_t ldx,
                           void* ws, size_t ws_bytes, am_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Dependence of two PAIRED sets (csrc/pair_dependence.hip, f32 tile engine): the row sums from which distance covariance /
+ * correlation and HSIC / CKA are formed, without an N x N matrix.  Row i of X (N x Dx) belongs to row i of Y (N x Dy); with
+ * `perm` (DEVICE, N entries) to row perm[i] of Y, addressed through the list - no gathered copy is made.  For every ordered
+ * pair i != j, dropped by INDEX (duplicated rows stay each other's pairs):
+ *   a_ij = k(x_i, x_j), b_ij = k(y_perm[i], y_perm[j]), k by `kernel` in the arithmetic of am_mmd_multi_f32 at scale 1
+ *     AM_MMD_ENERGY     +sqrt(d2)  (the distance: distance covariance; bandwidths ignored)
+ *     AM_MMD_GAUSSIAN   exp(-d2 g),        g = 0.5 / bw2
+ *     AM_MMD_LAPLACIAN  exp(-sqrt(d2) h),  h = 1.0 / sqrt(bw2)
+ *   with bw2 = bw2x on the X side and bw2y on the Y side, each (double)*bw2?_dev when that DEVICE float is given.
+ *   out_rows  DEVICE [N][5] doubles: A_i = sum_j a_ij, B_i = sum_j b_ij, H_i = sum_j a_ij b_ij, AA_i = sum_j a_ij^2,
+ *             BB_i = sum_j b_ij^2 - product and sums in f64
+ *   out_sums  DEVICE [8] doubles: sum A_i, sum B_i, sum H_i, sum AA_i, sum BB_i, sum A_i B_i, the number of finite rows, the
+ *             number of non-finite rows
+ * Both Grams of a 128 x 128 tile are formed in one workgroup, the X dot products parked as raw f32 accumulators while the Y
+ * slabs run; the full square is swept (every ordered pair once).  A row's sums are held per lane, folded in a fixed order and
+ * written per chunk of Q tiles (at most 16 chunks), the chunks added in chunk order: no floating-point atomics, two calls
+ * give the same bits, swapping the sets swaps A / B and AA / BB exactly.  A row with a non-finite element on either side
+ * makes every value it takes part in NaN and is counted in out_sums[7]; so is an entry of perm outside [0, N), which is
+ * never dereferenced.  X, Y: 16-byte aligned, ld % 4 == 0, ld >= D, N * ld * 4 < 4 GiB each; N >= 4; any Dx, Dy >= 1.  A null
+ * pointer, an unknown kernel, a misaligned set, or (Gaussian, Laplacian) a bandwidth that is neither given on the device nor
+ * finite and positive -> AM_ERR_BAD_ARG; bad sizes -> AM_ERR_BAD_SHAPE; AM_ERR_WORKSPACE names the size wanted (the norms, the
+ * offset table and 5 x chunks x 8 bytes per row: 64 MB at 100 000 rows).  Validated before the first HIP call;
+ * stream-ordered, no host synchronisation.
+ * ------------------------------------------------------------------------- */
+size_t am_pair_dependence_workspace_bytes(int64_t N, int Dx, int Dy);
+int am_pair_dependence_f32(const float* X, int64_t N, int64_t ldx, int Dx,
+                           const float* Y, int64_t ldy, int Dy,
+                           const int64_t* perm,            /* DEVICE [N] or NULL */
+                           int kernel, const float* bw2x_dev, double bw2x, const float* bw2y_dev, double bw2y,
+                           double* out_rows, double* out_sums,
+                           void* ws, size_t ws_bytes, am_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Kernel Audio Distance on float64 rows (csrc/kad_f64.hip, the f64 tile engine of the other *_f64 entry points: 64 x 64 tiles
  * on v_mfma_f64_16x16x4_f64).  The three calls above with `const double*` rows and the same argument lists; taken when BOTH
  * sets hold float64 rows.  Every step is f64: squared norms, the matrix-core dot product,
