@@ -17,71 +17,151 @@
 // = a per-tile base plus a compile-time constant; no index array lives in registers.  The two gates of KnnEpilogue are
 // kept on the VALUE (the list's last distance is the high word of its last key): the tile minimum, then __any per
 // element; after warm-up almost no tile reaches the 64-bit insert.  The gates are strict (d2 < last): a lane meets the
-// columns of its chunk in increasing order, so a value equal to the list's last distance always has the larger column
-// and loses the tie anyway; the insert itself compares whole keys.
+// columns of its chunk in increasing order and its list holds admissible columns only, so a value equal to the list's
+// last distance always has the larger column and loses the tie anyway; the insert itself compares whole keys.
 //
-// Self exclusion is by INDEX (column i + self_offset is skipped for row i; duplicates of a row stay its neighbours), and
-// only the tiles the shifted diagonal crosses run the variant of the epilogue that tests for it.
+// Which columns a row skips is a POLICY (ByIndex, ByLabel below): what the kernel is handed, what the epilogue keeps
+// for it, and three places of `finish`.  Everything else - the epilogue, the tile kernel's body with its two-pass list
+// join, the merge kernels, the entry's validation, workspace and norms - exists once.
 //
 // Column chunks: the (row block) x (column chunk) plan of the radii (work_item / choose_chunks of pairwise_common.h).
 // Partial lists: uint64 [nchunks][N][KCAP] in the caller's workspace; knn_search_merge_kernel takes the k smallest
 // keys of a row and writes sqrt_rn(d2) (or d2) and the column as int64, -1 where the distance is +inf (fewer than k
-// finite candidates: M < k, M - 1 < k with exclusion, non-finite rows).
+// finite candidates: M < k, fewer than k admissible columns, non-finite rows).
 //
 // Register budget (lists are 2 rows x KCAP keys x 2 registers per lane, beside 64 accumulators and the staging /
-// fragment registers of the pipeline; no instantiation uses scratch - tests/test_knn_search_cpu.py):
+// fragment registers of the pipeline; ByLabel has two label registers in place of ByIndex's diagonal bookkeeping; no
+// instantiation of either policy uses scratch - tests/test_knn_search_resources_cpu.py):
 //     KCAP  8:  32 list registers, __launch_bounds__(256, 2), two workgroups per CU
 //     KCAP 16:  64 list registers, __launch_bounds__(256, 2), two workgroups per CU
 //     KCAP 32: 128 list registers, __launch_bounds__(256, 1): ONE workgroup per CU (the lists alone are half of the 256
 //              registers a wave has at two per SIMD)
-#include "knn_keys.h"
+#include "row_sweep.h"
 
 namespace am {
 namespace search {
 
-constexpr size_t LDS_BYTES = (ENGINE_LDS_FLOATS + 2 * TB) * sizeof(float);   // staging slabs + [2][128] column norms
+constexpr int MAX_K = 32;
+constexpr unsigned long long EMPTY_KEY = 0x7f800000ffffffffull;          // (+inf, no column): larger than every real key
+constexpr unsigned INF_BITS = 0x7f800000u;
 
-template <int KCAP>
-struct KnnIndexEpilogue {
+__host__ __device__ constexpr int kcap_for(int k) { return k <= 8 ? 8 : k <= 16 ? 16 : 32; }
+
+// Branch-free sorted insertion of a key into an ascending list of CAP keys (list_insert of tile_engine.h on uint64:
+// compare-exchange down the list, fully unrolled).  A key >= best[CAP-1] falls through.
+template <int CAP>
+__device__ __forceinline__ void key_insert(unsigned long long (&best)[CAP], unsigned long long x) {
+#pragma unroll
+    for (int i = 0; i < CAP; ++i) {
+        const bool lt = x < best[i];
+        const unsigned long long lo = lt ? x : best[i];
+        x = lt ? best[i] : x;
+        best[i] = lo;
+    }
+}
+
+// ---- exclusion policies ----------------------------------------------------------------------------------------------------
+// A policy names the types of what only it needs - Labels: the label array of a side, as the kernel is handed it; Label: one
+// row's label in a register; SelfOffset: the shift of the excluded diagonal - and gives the other policy's the type Absent
+// (row_sweep.h), which takes no room: neither in the kernel's arguments nor in the epilogue.  So the one kernel and the one
+// epilogue below list every policy's arguments and members, each in ITS place: a label array beside the norms of its side, the
+// offset behind nchunks, the label registers behind the norm registers.  Both orders are part of the program - the kernarg
+// offsets of the parameter list, the order of the epilogue's members through the order in which the compiler promotes them to
+// registers - and gathered into one struct per policy, at one place, every instruction stream of this file moved
+// (profiles/exclusion_policy/isa_compare.txt).  ARRAYS: the per-column arrays a tile brings through LDS,
+// [2][ARRAYS][128] - array 0 is |y_j|^2 (+inf past the end).
+
+// Self exclusion by INDEX: column i + self_offset is skipped for row i (self_offset < 0: none; duplicates of a row stay
+// its neighbours), and only the tiles the shifted diagonal crosses run the variant of the gates that tests for it.
+struct ByIndex {
+    static constexpr bool BY_LABEL = false;
+    static constexpr int ARRAYS = 1;
+    using Labels = Absent;
+    using Label = Absent;
+    using SelfOffset = int64_t;
+};
+
+// A whole GROUP left out, by LABEL: every row of X and of Y carries one int32 label, and row i of X skips the rows of Y
+// whose label equals its own.  The embedding pipeline cuts every file into windows, so stored rows come in runs of
+// near-duplicates per track; with "row i itself, by index" as the only exclusion the nearest neighbour of almost every
+// window is a sibling window of its own song.
+//
+// Labels.  The column labels travel beside the column norms through LDS as array 1, the 32 bits of the label (the layout
+// of ColumnAux of row_sweep.h, staged by hand because array 1 is not a float: a label is only moved and compared for
+// equality, never computed with).  A lane keeps the labels of its two rows in two registers.  There is no diagonal:
+// which columns a row skips is not tied to its index.
+//
+// Gates.  Both gates - the tile minimum, then __any per element - run on the plain values and do not know about the
+// exclusion: they are supersets (a 32 x 32 sub-tile that holds a same-label pair closer than the row's list end always
+// passes the first one), which costs time and never a result, because the exclusion is applied where a key is made:
+// inside the wave-uniform insert loop, where one LDS word per candidate is read already,
+//     d2 = (label[column] == label[row]) ? +inf : clamp0(u)
+// and a key at +inf never displaces a finite one (the merge reports it as (+inf, -1)).  The gates stay strict: the
+// list holds admissible columns only, and the lane still meets them in increasing order.
+struct ByLabel {
+    static constexpr bool BY_LABEL = true;
+    static constexpr int ARRAYS = 2;
+    using Labels = const int32_t* __restrict__;
+    using Label = int32_t;
+    using SelfOffset = Absent;
+};
+
+template <class Excl>
+constexpr size_t LDS_BYTES = (ENGINE_LDS_FLOATS + 2 * Excl::ARRAYS * TB) * sizeof(float);   // staging slabs + [2][ARRAYS][128] column values
+
+template <int KCAP, class Excl>
+struct KnnListEpilogue {
     const float* qnorm;
+    typename Excl::Labels qgroup;
     int64_t nq;
-    float* aux;                          // LDS [2][128] : |y_j|^2 of the tile (+inf past nq)
-    int64_t self_lo;                     // column excluded for the first row of this row block (row r: self_lo + r); none: -2 * TB
+    float* aux;                          // LDS [2][ARRAYS][128] : |y_j|^2 of the tile (+inf past nq), then the labels' bits
+    typename Excl::SelfOffset self_lo;   // column excluded for the first row of this row block (row r: self_lo + r); none: -2 * TB
     float xn[2];
+    typename Excl::Label xg[2];          // the labels of the lane's two rows
     unsigned long long best[2][KCAP];
     float aux_reg;
+    typename Excl::Label aux_grp;
     const LaneInfo& L;
 
-    __device__ __forceinline__ KnnIndexEpilogue(const LaneInfo& l) : L(l) {}
+    __device__ __forceinline__ KnnListEpilogue(const LaneInfo& l) : L(l) {}
     __device__ __forceinline__ void aux_issue(int, int64_t qtile) {
         if (L.tid < TB) {
             const int64_t j = qtile * TB + L.tid;
             aux_reg = j < nq ? qnorm[j] : INFINITY;
+            if constexpr (Excl::BY_LABEL) aux_grp = j < nq ? qgroup[j] : 0;     // never looked at: such a pair is at +inf already
         }
     }
     __device__ __forceinline__ void aux_commit(int t) {
-        if (L.tid < TB) aux[(t & 1) * TB + L.tid] = aux_reg;
+        if (L.tid < TB) {
+            aux[(t & 1) * Excl::ARRAYS * TB + L.tid] = aux_reg;
+            if constexpr (Excl::BY_LABEL) reinterpret_cast<int32_t*>(aux)[(t & 1) * 2 * TB + TB + L.tid] = aux_grp;
+        }
     }
     __device__ __forceinline__ float last(int nt) const { return __uint_as_float((unsigned)(best[nt][KCAP - 1] >> 32)); }
 
     // The two gates run on values that are recomputed, not kept (16 more live registers cost the KCAP 16 form its second
-    // workgroup per CU), and unclamped: max(., 0) commutes with min, and a NaN loses every compare.  On a tile the shifted
-    // diagonal crosses (wave-uniform `diag`) the lane's excluded column counts as +inf.  Past the gates, the registers that
-    // may improve some lane's list are visited through a wave-uniform bit mask, so that the 64-bit insert is instantiated
-    // once per accumulator tile and not once per register (unrolled 16 times it pushed the KCAP 16 / 32 kernels over the
-    // unroll budget and their accumulators into scratch).  The mask is taken before the inserts tighten the list: a
-    // superset, and a key that no longer fits falls through the insert.
+    // workgroup per CU), and unclamped: max(., 0) commutes with min, and a NaN loses every compare.  ByIndex: on a tile the
+    // shifted diagonal crosses (wave-uniform `diag`) the lane's excluded column counts as +inf.  ByLabel: the gates see ALL
+    // columns, the row's own group included.  Past the gates, the registers that may improve some lane's list are visited
+    // through a wave-uniform bit mask, so that the 64-bit insert is instantiated once per accumulator tile and not once per
+    // register (unrolled 16 times it pushed the KCAP 16 / 32 kernels over the unroll budget and their accumulators into
+    // scratch).  The mask is taken before the inserts tighten the list: a superset, and a key that no longer fits falls
+    // through the insert.  Only in that loop is a column's label read and compared.
     __device__ __forceinline__ void finish(int t, int64_t qtile, f32x16 (&acc)[2][2]) {
-        const float* a = aux + (t & 1) * TB + L.wm * 64 + L.h * 4;
+        const float* a = aux + (t & 1) * Excl::ARRAYS * TB + L.wm * 64 + L.h * 4;
+        const int32_t* g = reinterpret_cast<const int32_t*>(a + TB);          // ByLabel: the labels of the lane's columns
         const int64_t c0 = qtile * TB + L.wm * 64 + L.h * 4;       // the lane's first column of the tile
         const unsigned cbase = (unsigned)c0;
-        const bool diag = qtile * TB < self_lo + TB && qtile * TB + TB > self_lo;
-        int srel[2] = {-1, -1};                                     // excluded column relative to c0 (-1: not in this tile)
-        if (diag) {
+        bool diag = false;
+        int srel[2] = {-1, -1};                                     // ByIndex: excluded column relative to c0 (-1: not in this tile)
+        if constexpr (!Excl::BY_LABEL) {
+            diag = qtile * TB < self_lo + TB && qtile * TB + TB > self_lo;
+            if (diag) {
 #pragma unroll
-            for (int nt = 0; nt < 2; ++nt) {
-                const int64_t rel = self_lo + sweep_row(0, L, nt) - c0;
-                srel[nt] = (rel >= 0 && rel < 64) ? (int)rel : -1;
+                for (int nt = 0; nt < 2; ++nt) {
+                    const int64_t rel = self_lo + sweep_row(0, L, nt) - c0;
+                    srel[nt] = (rel >= 0 && rel < 64) ? (int)rel : -1;
+                }
             }
         }
 #pragma unroll
@@ -93,7 +173,8 @@ struct KnnIndexEpilogue {
             for (int nt = 0; nt < 2; ++nt) {
                 auto value = [&](int reg, bool self_test) {
                     const float u = fmaf(-2.f, acc[mt][nt][reg], xn[nt] + yn[reg >> 2][reg & 3]);
-                    return (self_test && mt * 32 + (reg & 3) + 8 * (reg >> 2) == srel[nt]) ? INFINITY : u;   // the row itself: by index
+                    if constexpr (Excl::BY_LABEL) return u;
+                    else return (self_test && mt * 32 + (reg & 3) + 8 * (reg >> 2) == srel[nt]) ? INFINITY : u;   // the row itself: by index
                 };
                 float tmin = INFINITY;
                 if (diag) {
@@ -118,7 +199,10 @@ struct KnnIndexEpilogue {
 #pragma unroll
                         for (int q = 1; q < 16; ++q) p = (reg == q) ? acc[mt][nt][q] : p;
                         const float u = fmaf(-2.f, p, xn[nt] + a[rel]);
-                        const float d2 = rel == srel[nt] ? INFINITY : clamp0(u);
+                        bool skipped;
+                        if constexpr (Excl::BY_LABEL) skipped = g[rel] == xg[nt];      // the row's own group: by label
+                        else skipped = rel == srel[nt];
+                        const float d2 = skipped ? INFINITY : clamp0(u);
                         key_insert<KCAP>(best[nt], ((unsigned long long)(__float_as_uint(d2) & 0x7fffffffu) << 32) | (cbase + (unsigned)rel));
                     }
                 }
@@ -128,24 +212,29 @@ struct KnnIndexEpilogue {
 };
 
 // partial[(chunk * N + row) * KCAP + s] = s-th smallest key of `row` inside column chunk `chunk`
-template <int KCAP, bool KTAIL>
+template <int KCAP, bool KTAIL, class Excl>
 __global__ void __launch_bounds__(ENGINE_THREADS, KCAP <= 16 ? 2 : 1)
-knn_search_kernel(const float* __restrict__ X, int64_t N, int64_t ldx, const float* __restrict__ xnorm,
-                  const float* __restrict__ Y, int64_t M, int64_t ldy, const float* __restrict__ ynorm, int D, int nchunks,
-                  int64_t self_offset, unsigned long long* __restrict__ partial) {
+knn_search_kernel(const float* __restrict__ X, int64_t N, int64_t ldx, const float* __restrict__ xnorm, typename Excl::Labels xgroup,
+                  const float* __restrict__ Y, int64_t M, int64_t ldy, const float* __restrict__ ynorm, typename Excl::Labels ygroup,
+                  int D, int nchunks, typename Excl::SelfOffset self_offset, unsigned long long* __restrict__ partial) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const LaneInfo L;
     const WorkItem w = work_item((M + TB - 1) / TB, nchunks);
     const int chunk = blockIdx.x % nchunks;            // the chunk work_item gave this workgroup: its slice of `partial`
 
-    KnnIndexEpilogue<KCAP> epi(L);
+    KnnListEpilogue<KCAP, Excl> epi(L);
     epi.qnorm = ynorm;
     epi.nq = M;
     epi.aux = lds + ENGINE_LDS_FLOATS;
-    epi.self_lo = self_offset >= 0 ? w.prow0 + self_offset : -2 * TB;
+    if constexpr (Excl::BY_LABEL) epi.qgroup = ygroup;
+    else epi.self_lo = self_offset >= 0 ? w.prow0 + self_offset : -2 * TB;
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) {
         epi.xn[nt] = row_norm(xnorm, w.prow0, N, L, nt);
+        if constexpr (Excl::BY_LABEL) {
+            const int64_t i = sweep_row(w.prow0, L, nt);
+            epi.xg[nt] = i < N ? xgroup[i] : 0;            // (a row past the end is never stored)
+        }
 #pragma unroll
         for (int s = 0; s < KCAP; ++s) epi.best[nt][s] = EMPTY_KEY;
     }
@@ -204,33 +293,62 @@ __global__ void __launch_bounds__(256) knn_search_merge_kernel(const unsigned lo
     }
 }
 
-template <int KCAP>
-static int run_merge(const unsigned long long* partial, int64_t N, int nchunks, int k, int squared, float* out_dist, int64_t* out_idx,
-                     hipStream_t st) {
-    hipLaunchKernelGGL(knn_search_merge_kernel<KCAP>, dim3((unsigned)ceil_div(N, 256)), dim3(256), 0, st, partial, N, nchunks, k,
-                       squared, out_dist, out_idx);
+// ---- host side: the shapes a call takes, what its workspace holds, and one call ------------------------------------------
+static inline bool shape_ok(int64_t N, int64_t M, int D, int k) { return k >= 1 && k <= MAX_K && sweep_shape_ok(N, M, D, COLUMNS_KEYED); }
+
+struct Buffers {
+    float *xn, *yn;
+    unsigned long long* partial;
+};
+static inline void carve(Carver& c, int64_t N, int64_t M, int k, int nchunks, Buffers& b) {
+    b.xn = c.take<float>((size_t)N);
+    b.yn = c.take<float>((size_t)M);
+    b.partial = c.take<unsigned long long>((size_t)nchunks * (size_t)N * kcap_for(k));
+}
+
+template <int KCAP, class Excl>
+static int run(const float* X, int64_t N, int64_t ldx, const float* xn, typename Excl::Labels x_group, const float* Y, int64_t M,
+               int64_t ldy, const float* yn, typename Excl::Labels y_group, int D, int k, int nchunks,
+               typename Excl::SelfOffset self_offset, int squared, unsigned long long* partial, float* out_dist, int64_t* out_idx,
+               hipStream_t st) {
+    const int rc = launch_sweep(&knn_search_kernel<KCAP, false, Excl>, &knn_search_kernel<KCAP, true, Excl>, LDS_BYTES<Excl>, N, nchunks, D,
+                                st, X, N, ldx, xn, x_group, Y, M, ldy, yn, y_group, D, nchunks, self_offset, partial);
+    if (rc != AM_OK) return rc;
+    hipLaunchKernelGGL(knn_search_merge_kernel<KCAP>, dim3((unsigned)ceil_div(N, 256)), dim3(256), 0, st, partial, N, nchunks, k, squared,
+                       out_dist, out_idx);
     AM_LAUNCH_CHECK();
     return AM_OK;
 }
 
-// (knn_keys.h: the grouped search of knn_groups.hip merges its partial lists with the same kernel)
-int launch_merge(int kcap, const unsigned long long* partial, int64_t N, int nchunks, int k, int squared, float* out_dist,
-                 int64_t* out_idx, hipStream_t st) {
-    switch (kcap) {
-        case 8:  return run_merge<8>(partial, N, nchunks, k, squared, out_dist, out_idx, st);
-        case 16: return run_merge<16>(partial, N, nchunks, k, squared, out_dist, out_idx, st);
-        default: return run_merge<32>(partial, N, nchunks, k, squared, out_dist, out_idx, st);
+// validate, carve, norms, tile kernel, merge; `query` names the entry's workspace query in the error text
+template <class Excl>
+static int run_search(const float* X, int64_t N, int64_t ldx, typename Excl::Labels x_group, const float* Y, int64_t M, int64_t ldy,
+                      typename Excl::Labels y_group, int D, int k, typename Excl::SelfOffset self_offset, int squared, float* out_dist,
+                      int64_t* out_idx, void* ws, size_t ws_bytes, hipStream_t st, const char* query) {
+    int rc;
+    if ((rc = check_matrix(X, N, ldx, D, "X")) != AM_OK) return rc;
+    if ((rc = check_matrix(Y, M, ldy, D, "Y")) != AM_OK) return rc;
+    if constexpr (Excl::BY_LABEL)
+        AM_REQUIRE(x_group != nullptr && y_group != nullptr, AM_ERR_BAD_ARG, "%s is null", x_group == nullptr ? "x_group" : "y_group");
+    AM_REQUIRE(out_dist != nullptr && out_idx != nullptr, AM_ERR_BAD_ARG, "%s is null", out_dist == nullptr ? "out_dist" : "out_idx");
+    AM_REQUIRE(k >= 1 && k <= MAX_K, AM_ERR_BAD_SHAPE, "k = %d: the search keeps 1 .. %d neighbours per row", k, MAX_K);
+    AM_REQUIRE(shape_ok(N, M, D, k), AM_ERR_BAD_SHAPE, "N=%lld M=%lld: a column index takes 32 bits of a list key (M < 2^32 - 1)",
+               (long long)N, (long long)M);
+    const int nchunks = choose_chunks(N, M);
+    Carver c(ws, ws_bytes);
+    Buffers b;
+    carve(c, N, M, k, nchunks, b);
+    AM_REQUIRE(c.ok(), AM_ERR_WORKSPACE, "workspace too small: need %zu bytes (%s), have %zu", c.off, query, ws_bytes);
+    // a column past the end excludes nothing; the kernel adds row indices to the offset
+    if constexpr (!Excl::BY_LABEL)
+        if (self_offset >= M) self_offset = -1;
+    const float* yn;
+    if ((rc = launch_norms_pair(X, N, ldx, Y, M, ldy, D, b.xn, b.yn, st, &yn)) != AM_OK) return rc;
+    switch (kcap_for(k)) {
+        case 8:  return run<8, Excl>(X, N, ldx, b.xn, x_group, Y, M, ldy, yn, y_group, D, k, nchunks, self_offset, squared, b.partial, out_dist, out_idx, st);
+        case 16: return run<16, Excl>(X, N, ldx, b.xn, x_group, Y, M, ldy, yn, y_group, D, k, nchunks, self_offset, squared, b.partial, out_dist, out_idx, st);
+        default: return run<32, Excl>(X, N, ldx, b.xn, x_group, Y, M, ldy, yn, y_group, D, k, nchunks, self_offset, squared, b.partial, out_dist, out_idx, st);
     }
-}
-
-template <int KCAP>
-static int run(const float* X, int64_t N, int64_t ldx, const float* xn, const float* Y, int64_t M, int64_t ldy, const float* yn,
-               int D, int k, int nchunks, int64_t self_offset, int squared, unsigned long long* partial, float* out_dist,
-               int64_t* out_idx, hipStream_t st) {
-    const int rc = launch_sweep(&knn_search_kernel<KCAP, false>, &knn_search_kernel<KCAP, true>, LDS_BYTES, N, nchunks, D, st, X, N, ldx,
-                                xn, Y, M, ldy, yn, D, nchunks, self_offset, partial);
-    if (rc != AM_OK) return rc;
-    return run_merge<KCAP>(partial, N, nchunks, k, squared, out_dist, out_idx, st);
 }
 
 }  // namespace search
@@ -246,6 +364,9 @@ extern "C" size_t am_knn_search_workspace_bytes(int64_t N, int64_t M, int D, int
     return c.off;
 }
 
+// the labels are the caller's: nothing more to hold
+extern "C" size_t am_knn_search_groups_workspace_bytes(int64_t N, int64_t M, int D, int k) { return am_knn_search_workspace_bytes(N, M, D, k); }
+
 extern "C" int am_knn_search_chunks(int64_t N, int64_t M, int D, int k) {
     return search::shape_ok(N, M, D, k) ? choose_chunks(N, M) : 0;
 }
@@ -253,26 +374,13 @@ extern "C" int am_knn_search_chunks(int64_t N, int64_t M, int D, int k) {
 extern "C" int am_knn_search_f32(const float* X, int64_t N, int64_t ldx, const float* Y, int64_t M, int64_t ldy, int D, int k,
                                  int64_t self_offset, int squared, float* out_dist, int64_t* out_idx, void* ws, size_t ws_bytes,
                                  am_stream_t stream) {
-    int rc;
-    if ((rc = check_matrix(X, N, ldx, D, "X")) != AM_OK) return rc;
-    if ((rc = check_matrix(Y, M, ldy, D, "Y")) != AM_OK) return rc;
-    AM_REQUIRE(out_dist != nullptr && out_idx != nullptr, AM_ERR_BAD_ARG, "%s is null", out_dist == nullptr ? "out_dist" : "out_idx");
-    AM_REQUIRE(k >= 1 && k <= search::MAX_K, AM_ERR_BAD_SHAPE, "k = %d: the search keeps 1 .. %d neighbours per row", k, search::MAX_K);
-    AM_REQUIRE(search::shape_ok(N, M, D, k), AM_ERR_BAD_SHAPE, "N=%lld M=%lld: a column index takes 32 bits of a list key (M < 2^32 - 1)",
-               (long long)N, (long long)M);
-    const int nchunks = choose_chunks(N, M);
-    Carver c(ws, ws_bytes);
-    search::Buffers b;
-    search::carve(c, N, M, k, nchunks, b);
-    AM_REQUIRE(c.ok(), AM_ERR_WORKSPACE, "workspace too small: need %zu bytes (am_knn_search_workspace_bytes), have %zu", c.off, ws_bytes);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    // a column past the end excludes nothing; the kernel adds row indices to the offset
-    if (self_offset >= M) self_offset = -1;
-    const float* yn;
-    if ((rc = launch_norms_pair(X, N, ldx, Y, M, ldy, D, b.xn, b.yn, st, &yn)) != AM_OK) return rc;
-    switch (search::kcap_for(k)) {
-        case 8:  return search::run<8>(X, N, ldx, b.xn, Y, M, ldy, yn, D, k, nchunks, self_offset, squared, b.partial, out_dist, out_idx, st);
-        case 16: return search::run<16>(X, N, ldx, b.xn, Y, M, ldy, yn, D, k, nchunks, self_offset, squared, b.partial, out_dist, out_idx, st);
-        default: return search::run<32>(X, N, ldx, b.xn, Y, M, ldy, yn, D, k, nchunks, self_offset, squared, b.partial, out_dist, out_idx, st);
-    }
+    return search::run_search<search::ByIndex>(X, N, ldx, {}, Y, M, ldy, {}, D, k, self_offset, squared, out_dist, out_idx, ws, ws_bytes,
+                                               static_cast<hipStream_t>(stream), "am_knn_search_workspace_bytes");
+}
+
+extern "C" int am_knn_search_groups_f32(const float* X, int64_t N, int64_t ldx, const int32_t* x_group, const float* Y, int64_t M,
+                                        int64_t ldy, const int32_t* y_group, int D, int k, int squared, float* out_dist,
+                                        int64_t* out_idx, void* ws, size_t ws_bytes, am_stream_t stream) {
+    return search::run_search<search::ByLabel>(X, N, ldx, x_group, Y, M, ldy, y_group, D, k, {}, squared, out_dist, out_idx, ws, ws_bytes,
+                                               static_cast<hipStream_t>(stream), "am_knn_search_groups_workspace_bytes");
 }

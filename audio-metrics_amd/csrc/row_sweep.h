@@ -85,6 +85,16 @@ struct ColumnAux {
     __device__ __forceinline__ const float* tile(int t) const { return lds + (t & 1) * K * TB + L.wm * 64 + L.h * 4; }
 };
 
+// ---- what one variant of a kernel has and another has not ------------------------------------------------------------------
+// The type of a kernel parameter or an epilogue member in the instantiations that do not have it (the exclusion policies
+// of knn_search.hip and sample_scores.hip).  Its size is 0: as a kernel parameter it takes no room in the kernel
+// arguments (every other parameter keeps its offset), as a member no room in the struct.  It is only ever default-
+// constructed and passed on.
+struct Absent {
+    int none[0];
+};
+static_assert(sizeof(Absent) == 0, "Absent must take no room: it holds a place in kernel parameter lists and epilogues");
+
 // ---- reductions of a 256-thread merge kernel ----------------------------------------------------------------------------
 struct SumOp {
     template <class T>

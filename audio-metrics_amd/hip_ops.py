@@ -1290,14 +1290,22 @@ def knn_radii(x, k, columns=None, prepared=None):
 KNN_SEARCH_MAX_K = 32
 
 
-def knn_search(x, y, k, self_offset=None, squared=False):
-    """The k nearest rows of y for every row of x (am_knn_search_f32): (dist float32 [N, k] ascending, idx int64 [N, k]) as
-    device tensors, stream-ordered, nothing waits for the device.  Squared distances have the bits of the exact k-NN kernel
-    (column k of a (k + 1)-search is knn_radii(x, k, columns=y)); ties go to the smallest row index of y; `self_offset`:
-    column i + self_offset is skipped for row i (0 for x searched against itself, the shard's first row for a row shard),
-    by index - duplicate rows stay neighbours.  Missing neighbours (fewer than k finite candidates) are (+inf, -1)."""
+def _check_row_labels(x, y, x_group, y_group):
+    """The labels of the leave-group-out ops: int32 tensors, one label per row, on the device of their rows."""
+    for labels, rows, name in ((x_group, x, "x_group"), (y_group, y, "y_group")):
+        if not torch.is_tensor(labels) or labels.dtype != torch.int32:
+            raise ValueError(f"{name} must be an int32 tensor, got {getattr(labels, 'dtype', type(labels).__name__)}")
+        if labels.dim() != 1 or labels.shape[0] != rows.shape[0]:
+            raise ValueError(f"{name} must hold one label per row: shape {tuple(labels.shape)} for {rows.shape[0]} rows")
+        if labels.device != rows.device:
+            raise ValueError(f"{name} lives on {labels.device}, its rows on {rows.device}")
+
+
+def _knn_search(op, x, y, k, squared, self_offset=None, groups=None):
+    """knn_search (groups is None: exclusion by index) and knn_search_groups (groups = (x_group, y_group)); `op` names the
+    caller in the messages."""
     if is_f64(x) or is_f64(y):
-        raise NotImplementedError("knn_search takes float32 rows (the float64 matrix-core form is not implemented)")
+        raise NotImplementedError(f"{op} takes float32 rows (the float64 matrix-core form is not implemented)")
     k = int(k)
     if not 1 <= k <= KNN_SEARCH_MAX_K:
         raise ValueError(f"k={k} must be in 1 .. {KNN_SEARCH_MAX_K}")
@@ -1306,7 +1314,9 @@ def knn_search(x, y, k, self_offset=None, squared=False):
     if x.shape[1] != y.shape[1]:
         raise ValueError(f"feature widths differ: {x.shape[1]} and {y.shape[1]}")
     if x.shape[0] < 1 or y.shape[0] < 1:
-        raise ValueError(f"knn_search needs rows on both sides (got {x.shape[0]} and {y.shape[0]})")
+        raise ValueError(f"{op} needs rows on both sides (got {x.shape[0]} and {y.shape[0]})")
+    if groups is not None:
+        _check_row_labels(x, y, *groups)
     lib = _lib.load()
     same = x is y
     x = as_matrix(x, "x")
@@ -1316,11 +1326,28 @@ def knn_search(x, y, k, self_offset=None, squared=False):
     m = y.shape[0]
     dist = torch.empty((n, k), dtype=torch.float32, device=dev)
     idx = torch.empty((n, k), dtype=torch.int64, device=dev)
-    nb = lib.am_knn_search_workspace_bytes(n, m, d, k)
-    ws = _workspace(nb, dev)
-    _call(lib, "am_knn_search_f32", dev, _ptr(x), n, _ld(x), _ptr(y), m, _ld(y), d, k,
-          -1 if self_offset is None else int(self_offset), 1 if squared else 0, _ptr(dist), _ptr(idx), _ptr(ws), nb)
+    out = (1 if squared else 0, _ptr(dist), _ptr(idx))
+    if groups is None:
+        nb = lib.am_knn_search_workspace_bytes(n, m, d, k)
+        ws = _workspace(nb, dev)
+        _call(lib, "am_knn_search_f32", dev, _ptr(x), n, _ld(x), _ptr(y), m, _ld(y), d, k,
+              -1 if self_offset is None else int(self_offset), *out, _ptr(ws), nb)
+    else:
+        x_group, y_group = (g.contiguous() for g in groups)
+        nb = lib.am_knn_search_groups_workspace_bytes(n, m, d, k)
+        ws = _workspace(nb, dev)
+        _call(lib, "am_knn_search_groups_f32", dev, _ptr(x), n, _ld(x), _ptr(x_group), _ptr(y), m, _ld(y), _ptr(y_group), d, k,
+              *out, _ptr(ws), nb)
     return dist, idx
+
+
+def knn_search(x, y, k, self_offset=None, squared=False):
+    """The k nearest rows of y for every row of x (am_knn_search_f32): (dist float32 [N, k] ascending, idx int64 [N, k]) as
+    device tensors, stream-ordered, nothing waits for the device.  Squared distances have the bits of the exact k-NN kernel
+    (column k of a (k + 1)-search is knn_radii(x, k, columns=y)); ties go to the smallest row index of y; `self_offset`:
+    column i + self_offset is skipped for row i (0 for x searched against itself, the shard's first row for a row shard),
+    by index - duplicate rows stay neighbours.  Missing neighbours (fewer than k finite candidates) are (+inf, -1)."""
+    return _knn_search("knn_search", x, y, k, squared, self_offset=self_offset)
 
 
 def knn_search_groups(x, y, k, x_group, y_group, squared=False):
@@ -1330,39 +1357,7 @@ def knn_search_groups(x, y, k, x_group, y_group, squared=False):
     device; the bits of knn_search's distances; ties go to the smallest row index of y; (+inf, -1) where a row has fewer
     than k admissible finite candidates.  A set searched against itself with its own labels leaves out each row's whole
     group, the row included."""
-    if is_f64(x) or is_f64(y):
-        raise NotImplementedError("knn_search_groups takes float32 rows (the float64 matrix-core form is not implemented)")
-    k = int(k)
-    if not 1 <= k <= KNN_SEARCH_MAX_K:
-        raise ValueError(f"k={k} must be in 1 .. {KNN_SEARCH_MAX_K}")
-    if x.dim() != 2 or y.dim() != 2:
-        raise ValueError(f"x and y must be 2-D, got shapes {tuple(x.shape)} and {tuple(y.shape)}")
-    if x.shape[1] != y.shape[1]:
-        raise ValueError(f"feature widths differ: {x.shape[1]} and {y.shape[1]}")
-    if x.shape[0] < 1 or y.shape[0] < 1:
-        raise ValueError(f"knn_search_groups needs rows on both sides (got {x.shape[0]} and {y.shape[0]})")
-    for labels, rows, name in ((x_group, x, "x_group"), (y_group, y, "y_group")):
-        if not torch.is_tensor(labels) or labels.dtype != torch.int32:
-            raise ValueError(f"{name} must be an int32 tensor, got {getattr(labels, 'dtype', type(labels).__name__)}")
-        if labels.dim() != 1 or labels.shape[0] != rows.shape[0]:
-            raise ValueError(f"{name} must hold one label per row: shape {tuple(labels.shape)} for {rows.shape[0]} rows")
-        if labels.device != rows.device:
-            raise ValueError(f"{name} lives on {labels.device}, its rows on {rows.device}")
-    lib = _lib.load()
-    same = x is y
-    x = as_matrix(x, "x")
-    y = x if same else as_matrix(y, "y")
-    dev = _same_device(x, y)
-    x_group, y_group = x_group.contiguous(), y_group.contiguous()
-    n, d = x.shape
-    m = y.shape[0]
-    dist = torch.empty((n, k), dtype=torch.float32, device=dev)
-    idx = torch.empty((n, k), dtype=torch.int64, device=dev)
-    nb = lib.am_knn_search_groups_workspace_bytes(n, m, d, k)
-    ws = _workspace(nb, dev)
-    _call(lib, "am_knn_search_groups_f32", dev, _ptr(x), n, _ld(x), _ptr(x_group), _ptr(y), m, _ld(y), _ptr(y_group), d, k,
-          1 if squared else 0, _ptr(dist), _ptr(idx), _ptr(ws), nb)
-    return dist, idx
+    return _knn_search("knn_search_groups", x, y, k, squared, groups=(x_group, y_group))
 
 
 def knn_search_chunks(n, m, d, k):
@@ -1371,25 +1366,23 @@ def knn_search_chunks(n, m, d, k):
 
 
 # ---- per-sample realism, ball count and rarity on the PRDC manifold (csrc/sample_scores.hip) ----
-def sample_scores(x, y, r_y):
-    """Realism, ball count and rarity of every row of x against the rows of y and their k-NN radii r_y
-    (am_sample_scores_f32): (realism float32 [N], realism_index int64 [N], ball_count int32 [N], rarity float32 [N],
-    rarity_index int64 [N]) as device tensors, stream-ordered, nothing waits for the device.  realism = max_j r_j / |x - y_j|
-    (+inf on a row of y with a positive radius), ball_count = the balls the row lies in, with the bits of
-    prdc_counts(y, x, r_y, .)[0], rarity = the smallest radius among those balls (0 outside every ball); indices name rows
-    of y, ties go to the smallest, -1 where there is none.  A radius that is not > 0 is nobody's ball."""
+def _sample_scores(op, x, y, r_y, groups=None):
+    """sample_scores (groups is None: every pair counts) and sample_scores_groups (groups = (x_group, y_group)); `op` names
+    the caller in the messages."""
     if is_f64(x) or is_f64(y) or is_f64(r_y):
-        raise NotImplementedError("sample_scores takes float32 rows (the float64 matrix-core form is not implemented)")
+        raise NotImplementedError(f"{op} takes float32 rows (the float64 matrix-core form is not implemented)")
     if x.dim() != 2 or y.dim() != 2:
         raise ValueError(f"x and y must be 2-D, got shapes {tuple(x.shape)} and {tuple(y.shape)}")
     if x.shape[1] != y.shape[1]:
         raise ValueError(f"feature widths differ: {x.shape[1]} and {y.shape[1]}")
     if x.shape[0] < 1 or y.shape[0] < 1 or x.shape[1] < 1:
-        raise ValueError(f"sample_scores needs rows on both sides (got shapes {tuple(x.shape)} and {tuple(y.shape)})")
+        raise ValueError(f"{op} needs rows on both sides (got shapes {tuple(x.shape)} and {tuple(y.shape)})")
     if not torch.is_tensor(r_y) or r_y.dim() != 1 or r_y.shape[0] != y.shape[0] or r_y.dtype != torch.float32:
         raise ValueError(f"r_y must be a float32 tensor with one radius per row of y ({y.shape[0]}), got "
                          f"{tuple(r_y.shape) if torch.is_tensor(r_y) else type(r_y).__name__}"
                          f"{' ' + str(r_y.dtype) if torch.is_tensor(r_y) else ''}")
+    if groups is not None:
+        _check_row_labels(x, y, *groups)
     lib = _lib.load()
     same = x is y
     x = as_matrix(x, "x")
@@ -1404,11 +1397,28 @@ def sample_scores(x, y, r_y):
     count = torch.empty(n, dtype=torch.int32, device=dev)
     rarity = torch.empty(n, dtype=torch.float32, device=dev)
     rarity_idx = torch.empty(n, dtype=torch.int64, device=dev)
-    nb = lib.am_sample_scores_workspace_bytes(n, m, d)
-    ws = _workspace(nb, dev)
-    _call(lib, "am_sample_scores_f32", dev, _ptr(x), n, _ld(x), _ptr(y), m, _ld(y), d, _ptr(r_y), _ptr(realism),
-          _ptr(realism_idx), _ptr(count), _ptr(rarity), _ptr(rarity_idx), _ptr(ws), nb)
+    out = (_ptr(r_y), _ptr(realism), _ptr(realism_idx), _ptr(count), _ptr(rarity), _ptr(rarity_idx))
+    if groups is None:
+        nb = lib.am_sample_scores_workspace_bytes(n, m, d)
+        ws = _workspace(nb, dev)
+        _call(lib, "am_sample_scores_f32", dev, _ptr(x), n, _ld(x), _ptr(y), m, _ld(y), d, *out, _ptr(ws), nb)
+    else:
+        x_group, y_group = (g.contiguous() for g in groups)
+        nb = lib.am_sample_scores_groups_workspace_bytes(n, m, d)
+        ws = _workspace(nb, dev)
+        _call(lib, "am_sample_scores_groups_f32", dev, _ptr(x), n, _ld(x), _ptr(x_group), _ptr(y), m, _ld(y), _ptr(y_group), d,
+              *out, _ptr(ws), nb)
     return realism, realism_idx, count, rarity, rarity_idx
+
+
+def sample_scores(x, y, r_y):
+    """Realism, ball count and rarity of every row of x against the rows of y and their k-NN radii r_y
+    (am_sample_scores_f32): (realism float32 [N], realism_index int64 [N], ball_count int32 [N], rarity float32 [N],
+    rarity_index int64 [N]) as device tensors, stream-ordered, nothing waits for the device.  realism = max_j r_j / |x - y_j|
+    (+inf on a row of y with a positive radius), ball_count = the balls the row lies in, with the bits of
+    prdc_counts(y, x, r_y, .)[0], rarity = the smallest radius among those balls (0 outside every ball); indices name rows
+    of y, ties go to the smallest, -1 where there is none.  A radius that is not > 0 is nobody's ball."""
+    return _sample_scores("sample_scores", x, y, r_y)
 
 
 def sample_scores_chunks(n, m, d):
@@ -1424,45 +1434,7 @@ def sample_scores_groups(x, y, r_y, x_group, y_group):
     stream-ordered, nothing waits for the device; the bits of sample_scores on the admissible columns; ties go to the
     smallest row index of y; (0, -1, 0, 0.0, -1) for a row with no admissible reference row.  A set scored against itself
     with its own labels scores every row against the other groups."""
-    if is_f64(x) or is_f64(y) or is_f64(r_y):
-        raise NotImplementedError("sample_scores_groups takes float32 rows (the float64 matrix-core form is not implemented)")
-    if x.dim() != 2 or y.dim() != 2:
-        raise ValueError(f"x and y must be 2-D, got shapes {tuple(x.shape)} and {tuple(y.shape)}")
-    if x.shape[1] != y.shape[1]:
-        raise ValueError(f"feature widths differ: {x.shape[1]} and {y.shape[1]}")
-    if x.shape[0] < 1 or y.shape[0] < 1 or x.shape[1] < 1:
-        raise ValueError(f"sample_scores_groups needs rows on both sides (got shapes {tuple(x.shape)} and {tuple(y.shape)})")
-    if not torch.is_tensor(r_y) or r_y.dim() != 1 or r_y.shape[0] != y.shape[0] or r_y.dtype != torch.float32:
-        raise ValueError(f"r_y must be a float32 tensor with one radius per row of y ({y.shape[0]}), got "
-                         f"{tuple(r_y.shape) if torch.is_tensor(r_y) else type(r_y).__name__}"
-                         f"{' ' + str(r_y.dtype) if torch.is_tensor(r_y) else ''}")
-    for labels, rows, name in ((x_group, x, "x_group"), (y_group, y, "y_group")):
-        if not torch.is_tensor(labels) or labels.dtype != torch.int32:
-            raise ValueError(f"{name} must be an int32 tensor, got {getattr(labels, 'dtype', type(labels).__name__)}")
-        if labels.dim() != 1 or labels.shape[0] != rows.shape[0]:
-            raise ValueError(f"{name} must hold one label per row: shape {tuple(labels.shape)} for {rows.shape[0]} rows")
-        if labels.device != rows.device:
-            raise ValueError(f"{name} lives on {labels.device}, its rows on {rows.device}")
-    lib = _lib.load()
-    same = x is y
-    x = as_matrix(x, "x")
-    y = x if same else as_matrix(y, "y")
-    _require_cuda(r_y, "r_y")
-    dev = _same_device(x, y, r_y)
-    r_y = r_y.contiguous()
-    x_group, y_group = x_group.contiguous(), y_group.contiguous()
-    n, d = x.shape
-    m = y.shape[0]
-    realism = torch.empty(n, dtype=torch.float32, device=dev)
-    realism_idx = torch.empty(n, dtype=torch.int64, device=dev)
-    count = torch.empty(n, dtype=torch.int32, device=dev)
-    rarity = torch.empty(n, dtype=torch.float32, device=dev)
-    rarity_idx = torch.empty(n, dtype=torch.int64, device=dev)
-    nb = lib.am_sample_scores_groups_workspace_bytes(n, m, d)
-    ws = _workspace(nb, dev)
-    _call(lib, "am_sample_scores_groups_f32", dev, _ptr(x), n, _ld(x), _ptr(x_group), _ptr(y), m, _ld(y), _ptr(y_group), d, _ptr(r_y),
-          _ptr(realism), _ptr(realism_idx), _ptr(count), _ptr(rarity), _ptr(rarity_idx), _ptr(ws), nb)
-    return realism, realism_idx, count, rarity, rarity_idx
+    return _sample_scores("sample_scores_groups", x, y, r_y, groups=(x_group, y_group))
 
 
 # ---- probabilistic scoring rule of a point against a set (csrc/psr.hip) ----

@@ -641,7 +641,7 @@ int am_knn_search_f32(const float* X, int64_t N, int64_t ldx, const float* Y, in
                       void* ws, size_t ws_bytes, am_stream_t stream);
 
 /* ---------------------------------------------------------------------------
- * k-nearest-neighbour search that LEAVES A GROUP OUT (csrc/knn_groups.hip)       no counterpart in the reference
+ * k-nearest-neighbour search that LEAVES A GROUP OUT (csrc/knn_search.hip)       no counterpart in the reference
  *   Every row of X and of Y carries one int32 label (the song a window was cut from).  For every row i of X the k nearest
  *   rows of Y whose label DIFFERS from x_group[i]: column j is skipped for row i iff x_group[i] == y_group[j], for any
  *   int32 values (labels are moved and compared for equality, never computed with).  There is no self offset: a set
@@ -832,7 +832,7 @@ int am_sample_scores_f32(const float* X, int64_t N, int64_t ldx, const float* Y,
                          void* ws, size_t ws_bytes, am_stream_t stream);
 
 /* ---------------------------------------------------------------------------
- * PER-SAMPLE realism, ball count and rarity that LEAVE A GROUP OUT (csrc/sample_scores_groups.hip)   no counterpart in the reference
+ * PER-SAMPLE realism, ball count and rarity that LEAVE A GROUP OUT (csrc/sample_scores.hip)   no counterpart in the reference
  *   am_sample_scores_f32 with one int32 label per row of X and per row of Y (the song a window was cut from).  A pair
  *   (i, j) with x_group[i] == y_group[j] is NO PAIR, for any int32 values (labels are moved and compared for equality,
  *   never computed with): it is not counted, its ratio is 0, it is no candidate of the rarity.

@@ -1,4 +1,4 @@
-"""Numpy-float32 restatement of the leave-group-out PRDC, per-sample scores and authenticity (csrc/sample_scores_groups.hip,
+"""Numpy-float32 restatement of the leave-group-out PRDC, per-sample scores and authenticity (csrc/sample_scores.hip,
 metrics/prdc_groups.py): the oracle of tests/test_gpu_sample_scores_groups.py and tests/test_prdc_groups_cpu.py.  Nothing here
 imports the package.
 

@@ -1,21 +1,16 @@
 """The leave-group-out nearest-neighbour search and what stands on it, the part that needs no GPU: validation before any
 device call (hip_ops.knn_search_groups, nearest_neighbors(groups=...), nearest_neighbor_two_sample_test), the new names in
-header / signature table / package, the C entry's error codes and workspace query, and the compile-time resources of
-csrc/knn_groups.hip (no scratch memory in any instantiation, two workgroups per CU for the lists of 8 and 16 keys, one for
-the lists of 32)."""
+header / signature table / package, the C entry's error codes and workspace query.  (The compile-time resources of the
+by-label kernels: test_knn_search_resources_cpu.py.)"""
 import ctypes
 import os
 import re
-import shutil
 
 import numpy as np
 import pytest
 import torch
 
-from test_knn_search_resources_cpu import resource_usage
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "audio-metrics_amd", "csrc")
 BAD_ARG, BAD_SHAPE, WORKSPACE = -1, -2, -4
 FAKE = ctypes.c_void_p(0x10000)                       # 16-byte aligned, never dereferenced: the calls stop at validation
 NAMES = ("am_knn_search_groups_workspace_bytes", "am_knn_search_groups_f32")
@@ -212,22 +207,3 @@ def test_workspace_query(lib):
         assert lists + (n + m) * 4 <= nb <= lists + (n + m) * 4 + 3 * 256, (k, nb)
         assert nb == lib.am_knn_search_workspace_bytes(n, m, 64, k)          # the labels are the caller's: nothing more to hold
     assert lib.am_knn_search_groups_workspace_bytes(3, 2, 8, 5) > 0
-
-
-@pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"), reason="hipcc not available")
-def test_grouped_kernels_keep_their_workgroups_per_cu_and_use_no_scratch():
-    usage = resource_usage("knn_groups.hip")
-    with open(os.path.join(CSRC, "knn_groups.hip")) as f:
-        source = f.read()
-    assert re.findall(r"\b(\w+_kernel)\(const", source) == ["knn_groups_kernel"]       # ONE merge kernel: that of knn_search.hip
-    assert source.count("__global__") == 1 and "launch_merge(" in source and "asm" not in source
-    assert "__launch_bounds__(ENGINE_THREADS, KCAP <= 16 ? 2 : 1)" in source
-    tile = {n: u for n, u in usage.items() if re.search(r"knn_groups_kernelILi(8|16|32)ELb[01]E", n)}
-    assert sorted(re.search(r"ILi(\d+)ELb([01])E", n).groups() for n in tile) == \
-        sorted((str(k), t) for k in (8, 16, 32) for t in "01"), sorted(tile)
-    assert len(usage) == 6, sorted(usage)                                      # every __global__ kernel of the file
-    for n, u in tile.items():
-        print(n, u)
-        kcap = int(re.search(r"ILi(\d+)E", n).group(1))
-        assert u["scratch"] == 0, (n, u)
-        assert u["vgprs"] <= 256 and u["occupancy"] >= (2 if kcap <= 16 else 1), (n, u)

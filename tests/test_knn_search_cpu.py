@@ -5,14 +5,13 @@ per CU for the lists of 8 and 16 keys)."""
 import ctypes
 import os
 import re
-import shutil
-import subprocess
 
 import pytest
 import torch
 
+from kernel_resources import needs_hipcc, resource_usage
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "audio-metrics_amd", "csrc")
 BAD_ARG, BAD_SHAPE, WORKSPACE = -1, -2, -4
 FAKE = ctypes.c_void_p(0x10000)                       # 16-byte aligned, never dereferenced: the calls stop at validation
 NAMES = ("am_knn_search_workspace_bytes", "am_knn_search_chunks", "am_knn_search_f32")
@@ -121,35 +120,19 @@ def test_workspace_and_chunk_queries(lib):
     assert lib.am_knn_search_workspace_bytes(3, 2, 8, 5) > 0             # fewer rows than k is allowed: (+inf, -1) entries
 
 
-@pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"), reason="hipcc not available")
+@needs_hipcc
 def test_knn_search_kernels_use_no_scratch_memory():
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("am_build", os.path.join(ROOT, "audio-metrics_amd", "_build.py"))
-    build = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(build)                                         # the flags the shipped library is built with
-    r = subprocess.run([hipcc, *build.HIPCC_FLAGS, "--cuda-device-only", "-c", "knn_search.hip", "-o", os.devnull,
-                        "-Rpass-analysis=kernel-resource-usage"], cwd=CSRC, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    usage, name = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            usage[name] = {}
-        for key, short in (("ScratchSize \\[bytes/lane\\]", "scratch"), ("VGPRs", "vgprs"), ("Occupancy \\[waves/SIMD\\]", "occupancy")):
-            m = re.search(r"remark:\s+%s: (\d+)" % key, line)
-            if m and name:
-                usage[name][short] = int(m.group(1))
+    usage = resource_usage("knn_search.hip")
     search = {n: u for n, u in usage.items() if "knn_search" in n}
-    # tile kernel: lists of 8 / 16 / 32 keys x with / without an inner-dimension tail; merge kernel: one per list length
+    # tile kernel: lists of 8 / 16 / 32 keys x with / without an inner-dimension tail x exclusion by index / by label;
+    # merge kernel: one per list length
     tile = {n: u for n, u in search.items() if "knn_search_kernel" in n}
     merge = {n: u for n, u in search.items() if "knn_search_merge_kernel" in n}
-    assert len(tile) == 6 and len(merge) == 3 and len(search) == 9, sorted(usage)
+    assert len(tile) == 12 and len(merge) == 3 and len(search) == 15, sorted(usage)
     for n, u in search.items():
         assert u["scratch"] == 0, (n, u)
     for cap in (8, 16):
         hits = {n: u for n, u in tile.items() if "ILi%dELb" % cap in n}
-        assert len(hits) == 2, (cap, sorted(tile))
+        assert len(hits) == 4, (cap, sorted(tile))
         for n, u in hits.items():
             assert u["vgprs"] <= 256 and u["occupancy"] >= 2, (n, u)       # two workgroups of four waves per CU

@@ -1,47 +1,35 @@
-"""The compile-time resources of csrc/sample_scores.hip, as the shipped flags build it: both instantiations of the tile
-kernel (without / with the inner-dimension tail) keep two workgroups of four waves on a CU (at most 256 VGPRs, occupancy
->= 2) and no kernel of the file uses scratch memory - two 64-bit keys, a count and a gated division per lane and row must
-not cost registers the accumulator tile needs."""
-import importlib.util
-import os
+"""The compile-time resources of csrc/sample_scores.hip, as the shipped flags build it: the four instantiations of the tile
+kernel (without / with the inner-dimension tail, every pair counting / equal labels being no pair) keep two workgroups of
+four waves on a CU (at most 256 VGPRs, occupancy >= 2, 2 x 75 KiB resp. 2 x 76 KiB of LDS inside the 160 KiB of a CU) and
+no kernel of the file uses scratch memory - two 64-bit keys, a count and a gated division per lane and row, and with labels
+two label registers and a fourth column array, must not cost registers the accumulator tile needs.  Both policies share
+the column pre-kernel and the merge kernel."""
 import re
-import shutil
-import subprocess
 
-import pytest
+from kernel_resources import needs_hipcc, read_source, resource_usage
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "audio-metrics_amd", "csrc")
+POLICIES = {"AllPairs": 3, "OtherLabels": 4}                               # policy -> per-column arrays through LDS
 
 
-@pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"), reason="hipcc not available")
-def test_tile_kernels_keep_two_workgroups_per_cu_and_use_no_scratch():
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    spec = importlib.util.spec_from_file_location("am_build", os.path.join(ROOT, "audio-metrics_amd", "_build.py"))
-    build = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(build)                                         # the flags the shipped library is built with
-    r = subprocess.run([hipcc, *build.HIPCC_FLAGS, "--cuda-device-only", "-c", "sample_scores.hip", "-o", os.devnull,
-                        "-Rpass-analysis=kernel-resource-usage"], cwd=CSRC, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    usage, name = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            usage[name] = {}
-        for key, short in (("ScratchSize \\[bytes/lane\\]", "scratch"), ("VGPRs", "vgprs"), ("Occupancy \\[waves/SIMD\\]", "occupancy")):
-            m = re.search(r"remark:\s+%s: (\d+)" % key, line)
-            if m and name:
-                usage[name][short] = int(m.group(1))
-    with open(os.path.join(CSRC, "sample_scores.hip")) as f:
-        source = f.read()
-    declared = set(re.findall(r"\b(\w*scores\w*_kernel)\(", source))
-    assert declared == {"scores_columns_kernel", "sample_scores_kernel", "sample_scores_merge_kernel"}, declared
+@needs_hipcc
+def test_tile_kernels_of_both_policies_keep_two_workgroups_per_cu_and_use_no_scratch():
+    usage = resource_usage("sample_scores.hip")
+    source = read_source("sample_scores.hip")
+    declared = re.findall(r"\b(\w+_kernel)\(const", source)
+    assert declared == ["scores_columns_kernel", "sample_scores_kernel", "sample_scores_merge_kernel"], declared
+    assert source.count("__global__") == 3 and "asm" not in source
     assert "__launch_bounds__(ENGINE_THREADS, 2)" in source
+    # staging slabs + [2][ARRAYS][128] floats, ARRAYS from the policy; that two workgroups fit in a CU's LDS under both is
+    # checked where ENGINE_LDS_FLOATS is known, by the compiler (the build of `usage` above went through it)
+    assert "(ENGINE_LDS_FLOATS + 2 * Excl::ARRAYS * TB) * sizeof(float)" in source
+    assert "static_assert(2 * LDS_BYTES<AllPairs> <= 160 * 1024 && 2 * LDS_BYTES<OtherLabels> <= 160 * 1024," in source
+    for policy, arrays in POLICIES.items():
+        assert re.search(r"struct %s \{[^}]*static constexpr int ARRAYS = %d;" % (policy, arrays), source), policy
     tile = {n: u for n, u in usage.items() if "sample_scores_kernel" in n}
-    # the tile kernel without / with the inner-dimension tail
-    assert len(tile) == 2 and sum("ILb0E" in n for n in tile) == 1 and sum("ILb1E" in n for n in tile) == 1, sorted(tile)
-    assert len(usage) == 4 and all(any(k in n for n in usage) for k in declared), sorted(usage)      # every __global__ kernel of the file
+    # the tile kernel without / with the inner-dimension tail under either policy
+    assert sorted(re.search(r"ILb([01])ENS\d_\d+(\w+?)EEE", n).groups() for n in tile) == \
+        sorted((t, p) for t in "01" for p in POLICIES), sorted(tile)
+    assert len(tile) == 4 and len(usage) == 6 and all(any(k in n for n in usage) for k in declared), sorted(usage)   # every __global__ kernel
     for n, u in usage.items():
         print(n, u)
         assert u["scratch"] == 0, (n, u)

@@ -1,12 +1,16 @@
 #!/usr/bin/env python3
 """Compare the instruction streams of the kernels in two device assembly files (hipcc --cuda-device-only -S).
 
-    python tools/isa_compare.py parent.s change.s [name-substring]
+    python tools/isa_compare.py parent.s change.s [name-substring] [old=new ...]
 
 Each file is split at its kernel labels; comments, directives and blank lines are dropped, and what remains of each kernel
 (instructions and local labels) is compared text for text; a local label .LBB<f>_<n> is read without <f>, the position of its
 function in the file, which moves when a function is added or removed above it.  For a kernel that differs the differing
-lines and the counts of the instructions that make up a pipeline stage are printed.  Exit status 0: the same kernels, every one identical."""
+lines and the counts of the instructions that make up a pipeline stage are printed.  Exit status 0: the same kernels, every one identical.
+
+Kernels are paired by their mangled names.  Where a change renamed a kernel or gave it other template or function parameters,
+each argument old=new replaces the substring `old` by `new` in the names of the FIRST file before the pairing, e.g.
+17knn_groups_kernel=17knn_search_kernel; without such arguments names are compared as they are."""
 import difflib
 import re
 import sys
@@ -47,7 +51,12 @@ def counts(body):
 
 
 def main():
-    a, b = kernels(sys.argv[1], sys.argv[3] if len(sys.argv) > 3 else ""), kernels(sys.argv[2], sys.argv[3] if len(sys.argv) > 3 else "")
+    renames = [arg.split("=", 1) for arg in sys.argv[3:] if "=" in arg]
+    want = next((arg for arg in sys.argv[3:] if "=" not in arg), "")
+    a, b = kernels(sys.argv[1], ""), kernels(sys.argv[2], want)
+    for old, new in renames:
+        a = {name.replace(old, new): body for name, body in a.items()}
+    a = {name: body for name, body in a.items() if want in name}
     bad = 0
     for name in sorted(set(a) | set(b)):
         if name not in a or name not in b:
