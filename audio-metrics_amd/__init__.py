@@ -41,6 +41,7 @@ from .metrics.c2st import classifier_two_sample_test, c2st_folds, c2st_summary, 
 from .metrics.nn_test import nearest_neighbor_two_sample_test, nn_permutation_null   # noqa: F401
 from .metrics.dependence import (distance_correlation, kernel_alignment, dependence_from_sums,   # noqa: F401
                                  dependence_permutations, row_dependence, dcor_t_test)
+from .metrics.retrieval import retrieval_scores, retrieval_summary            # noqa: F401
 
 from .embed import ItemCategory, embedding_pipeline                            # noqa: F401
 from .projection import IncrementalPCA                                         # noqa: F401

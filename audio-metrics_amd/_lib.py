@@ -127,6 +127,10 @@ SIGNATURES = {
     "am_psr_workspace_bytes":(c_size_t, [c_int64, c_int64, c_int]),
     "am_psr_chunks": (c_int, [c_int64, c_int64, c_int]),
     "am_psr_f32": (c_int, [_P, c_int64, c_int64, _P, c_int64, c_int64, c_int, c_double, _P, _P, _P, _P, c_size_t, _P]),
+    "am_retrieval_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int]),
+    "am_retrieval_chunks": (c_int, [c_int64, c_int64, c_int]),
+    "am_retrieval_ranks_f32": (c_int, [_P, c_int64, c_int64, _P, c_int64, c_int64, c_int, c_int, _P, _P, _P, c_int64, _P, _P,
+                                       _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
     "am_kmeans_update_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int]),
     "am_kmeans_update_f32": (c_int, [_P, c_int64, c_int64, c_int, _P, _P, _P, c_int64, _P, c_int64, _P, c_int64, _P, _P, c_size_t,
                                      _P]),

@@ -1481,6 +1481,71 @@ def psr_chunks(n, m, d):
     return int(_lib.load().am_psr_chunks(int(n), int(m), int(d)))
 
 
+# ---- retrieval ranks of paired sets (csrc/retrieval.hip) ----
+def _check_segments(q, pos_start, pos_count, pos_columns):
+    """The positives of retrieval_ranks: int64 tensors on the device of the rows, one start and one count per query row."""
+    for t, name in ((pos_start, "pos_start"), (pos_count, "pos_count"), (pos_columns, "pos_columns")):
+        if not torch.is_tensor(t) or t.dtype != torch.int64 or t.dim() != 1:
+            raise ValueError(f"{name} must be a 1-D int64 tensor, got {getattr(t, 'dtype', type(t).__name__)}"
+                             f"{' of shape ' + str(tuple(t.shape)) if torch.is_tensor(t) else ''}")
+        if t.device != q.device:
+            raise ValueError(f"{name} lives on {t.device}, the rows on {q.device}")
+    for t, name in ((pos_start, "pos_start"), (pos_count, "pos_count")):
+        if t.shape[0] != q.shape[0]:
+            raise ValueError(f"{name} must hold one entry per query row: {t.shape[0]} for {q.shape[0]} rows")
+
+
+def retrieval_ranks(q, g, pos_start, pos_count, pos_columns, cosine=True, groups=None):
+    """The rank of every query row's best positive among the rows of g (am_retrieval_ranks_f32): (better int32 [N], tied
+    int32 [N], score float32 [N], positive int64 [N], n_pos int32 [N], n_pos_own_group int32 [N]) as device tensors,
+    stream-ordered, nothing waits for the device.  The positives of row i are the columns
+    pos_columns[pos_start[i] : pos_start[i] + pos_count[i]] (int64 device tensors; distinct columns inside a segment).  A
+    pair scores u = <q_i, g_j> * w_j with the bits of the exact tile engine, w_j = 1 / |g_j| (cosine) or 1 (dot), correctly
+    rounded; a NaN u is no score.  t = the best scored positive, `positive` the smallest column reaching it, better / tied =
+    the negatives with u > t / u == t, score = t (dot) or the cosine itself; rank = 1 + better.  A row without a scored
+    positive, or with a positive outside [0, M), is unranked: (-1, -1, NaN, -1).  groups = (q_group, g_group), int32 device
+    vectors: a column of the row's own group is no negative (a positive there is still a positive).  `q is g` computes the
+    norms once.  Two calls return the same bits."""
+    if is_f64(q) or is_f64(g):
+        raise NotImplementedError("retrieval_ranks takes float32 rows (the float64 matrix-core form is not implemented)")
+    if q.dim() != 2 or g.dim() != 2:
+        raise ValueError(f"q and g must be 2-D, got shapes {tuple(q.shape)} and {tuple(g.shape)}")
+    if q.shape[1] != g.shape[1]:
+        raise ValueError(f"feature widths differ: {q.shape[1]} and {g.shape[1]}")
+    if q.shape[0] < 1 or g.shape[0] < 1 or q.shape[1] < 1:
+        raise ValueError(f"retrieval_ranks needs rows on both sides (got shapes {tuple(q.shape)} and {tuple(g.shape)})")
+    if groups is not None:
+        _check_row_labels(q, g, *groups)
+    lib = _lib.load()
+    same = q is g
+    q = as_matrix(q, "q")
+    g = q if same else as_matrix(g, "g")
+    dev = _same_device(q, g)
+    _check_segments(q, pos_start, pos_count, pos_columns)
+    pos_start, pos_count, pos_columns = pos_start.contiguous(), pos_count.contiguous(), pos_columns.contiguous()
+    n, d = q.shape
+    m = g.shape[0]
+    better = torch.empty(n, dtype=torch.int32, device=dev)
+    tied = torch.empty(n, dtype=torch.int32, device=dev)
+    score = torch.empty(n, dtype=torch.float32, device=dev)
+    positive = torch.empty(n, dtype=torch.int64, device=dev)
+    n_pos = torch.empty(n, dtype=torch.int32, device=dev)
+    n_pos_own = torch.empty(n, dtype=torch.int32, device=dev)
+    q_group, g_group = (t.contiguous() for t in groups) if groups is not None else (None, None)
+    nb = lib.am_retrieval_workspace_bytes(n, m, d)
+    ws = _workspace(nb, dev)
+    _call(lib, "am_retrieval_ranks_f32", dev, _ptr(q), n, _ld(q), _ptr(g), m, _ld(g), d, 1 if cosine else 0,
+          _ptr(pos_start), _ptr(pos_count), _ptr(pos_columns) if pos_columns.numel() else None, int(pos_columns.numel()),
+          _ptr(q_group) if groups is not None else None, _ptr(g_group) if groups is not None else None,
+          _ptr(better), _ptr(tied), _ptr(score), _ptr(positive), _ptr(n_pos), _ptr(n_pos_own), _ptr(ws), nb)
+    return better, tied, score, positive, n_pos, n_pos_own
+
+
+def retrieval_chunks(n, m, d):
+    """Column chunks the plan cuts the rows of g into (am_retrieval_chunks; tests and tools)."""
+    return int(_lib.load().am_retrieval_chunks(int(n), int(m), int(d)))
+
+
 # ---- k-means: the two halves of a Lloyd iteration (csrc/kmeans.hip) ----
 def _kmeans_check(what, x, c):
     if is_f64(x) or is_f64(c):

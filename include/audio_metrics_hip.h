@@ -892,6 +892,42 @@ int am_psr_f32(const float* X, int64_t N, int64_t ldx, const float* Y, int64_t M
                void* ws, size_t ws_bytes, am_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * RETRIEVAL RANKS of paired sets (csrc/retrieval.hip)                                no counterpart in the reference
+ *   At which rank does query row i find its own gallery rows among all M?  Q: the queries (N rows), G: the gallery (M
+ *   rows); the POSITIVES of row i are the columns pos_columns[pos_start[i] .. pos_start[i] + pos_count[i]) - int64 device
+ *   arrays, distinct columns inside a segment, rows with one label may share a segment.  One Gram pass on the exact f32
+ *   tile engine, no N x M matrix.  Per pair:
+ *     u_ij = fmul_rn(a_ij, w_j),  a_ij = <q_i, g_j> with the bits of the tile engine (the fmaf chain of am_knn_search_f32),
+ *            w_j = 1 (cosine == 0) or fdiv_rn(1, sqrt_rn(|g_j|^2)) (cosine != 0; the f32 norms of the search).  The query's
+ *            own norm changes no order inside its row and is not applied.  A pair whose u is NaN HAS NO SCORE (a zero-norm
+ *            gallery row under cosine, a row with a non-finite element): it is never a positive and never counted
+ *   Outputs per row i of Q, all overwritten:
+ *     out_positive[i]  the smallest positive column that reaches t_i = max { u_ij : j in P_i, scored }; -1 for an UNRANKED
+ *                      row: one with no scored positive, with an entry of its segment outside [0, M) or with a segment
+ *                      that leaves pos_columns (nothing out of range is dereferenced)
+ *     out_better[i]    #{ negatives j : u_ij >  t_i }, out_tied[i] = #{ negatives j : u_ij == t_i } as IEEE float compares;
+ *                      the NEGATIVES are the columns not in P_i and, with group ids, those with g_group[j] != q_group[i];
+ *                      -1, -1 for an unranked row.  rank = 1 + out_better is the optimistic convention
+ *     out_score[i]     t_i (dot), fmul_rn(t_i, w_i^Q) with the query's own weight (cosine: the cosine itself); NaN unranked
+ *     out_n_pos[i]     the entries of the row's segment inside [0, M); out_n_pos_own_group[i] those of them with
+ *                      g_group[j] == q_group[i] (0 without group ids)
+ *   q_group, g_group: int32 device vectors, BOTH null (every column that is no positive is a negative) or both set; exactly
+ *   one null -> AM_ERR_BAD_ARG.  A positive inside the row's own group is still a positive.  No atomics: two calls return
+ *   the same bits, whatever the chunk plan (am_retrieval_chunks) and the order of a segment's entries.  M < 2^31 (the
+ *   counts are int32); Q, G as for am_knn_search_f32 (16-byte aligned, ld % 4 == 0, ld >= D); Q may be G.  Workspace: the
+ *   norms and weights of both sides, t_i, and [am_retrieval_chunks][N] int32 x 2 partials; the query returns 0 for a shape
+ *   the call refuses.  Everything is validated before the first HIP call; the call is asynchronous.
+ * ------------------------------------------------------------------------- */
+size_t am_retrieval_workspace_bytes(int64_t N, int64_t M, int D);
+int am_retrieval_chunks(int64_t N, int64_t M, int D);          /* column chunks of the plan (tests, tools) */
+int am_retrieval_ranks_f32(const float* Q, int64_t N, int64_t ldq, const float* G, int64_t M, int64_t ldg, int D, int cosine,
+                           const int64_t* pos_start, const int64_t* pos_count, const int64_t* pos_columns,
+                           int64_t n_pos_columns, const int32_t* q_group, const int32_t* g_group,
+                           int32_t* out_better, int32_t* out_tied, float* out_score, int64_t* out_positive,
+                           int32_t* out_n_pos, int32_t* out_n_pos_own_group,
+                           void* ws, size_t ws_bytes, am_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * SLICED WASSERSTEIN distance, its three device steps (csrc/swd.hip)                 no counterpart in the reference
  *   Every pointer below is a DEVICE pointer.  Everything is validated before the first HIP call; the calls are
  *   asynchronous.  No floating-point atomics: two calls return the same bits.
