@@ -3,11 +3,21 @@
 PyTorch is used only as the device-memory allocator and stream owner; every
 computation below is a call into libaudio_metrics_hip.so on torch's current
 HIP stream.  There is no CPU path: CPU tensors are rejected.
+
+Every operation is written on a few helpers: _rows(e, name, f64) gives a set's matrix form, its leading dimension and the
+entry-point suffix; _any_f64 / _both_f64 are the two float64 promotion rules; _refuse_f64, _check_two_sets and _two_sets are
+the preamble of the float32 row-sweep ops, _check_gram_rows and _blocks_mask that of the Gram ops; _opt / _host turn optional
+tensors / host arrays into pointers; _run(name, dev, query, query_args, *args) asks the workspace query, allocates and calls.
+Binding a new entry point am_new_f32 / _f64 with its am_new_workspace_bytes(n, d) takes, after its argument checks:
+    rows, ld, kind = _rows(rows, "rows", is_f64(rows))
+    out = torch.empty(rows.shape[0], dtype=torch.float64, device=rows.device)
+    _run("am_new_" + kind, rows.device, "am_new_workspace_bytes", rows.shape, _ptr(rows), *rows.shape, ld, _opt(weights), _ptr(out))
 """
 import ctypes
 import math
-import os
+import struct
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -22,11 +32,29 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr())
 
 
+def _opt(t):
+    """The device pointer of an optional tensor: NULL for None."""
+    return _ptr(t) if t is not None else ctypes.c_void_p(None)
+
+
+def _host(a):
+    """The pointer to a host ctypes array, NULL for None."""
+    return ctypes.cast(a, ctypes.c_void_p) if a is not None else ctypes.c_void_p(None)
+
+
 def _workspace(nbytes, device):
     return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
 
 
 _SIDE_STREAMS = {}
+
+
+def _side_stream(key, dev):
+    """The side stream kept under `key`, created on `dev` at its first use."""
+    side = _SIDE_STREAMS.get(key)
+    if side is None:
+        side = _SIDE_STREAMS[key] = torch.cuda.Stream(dev)
+    return side
 
 
 def upload_host_array(array, device):
@@ -36,14 +64,11 @@ def upload_host_array(array, device):
     `Tensor.pin_memory()` per call and kernels reading a pooled pinned buffer in place stall the host for 75-100 ms
     every few calls (measured on the 2 x 800 KB kernel-distance index tables: a 10 ms evaluate became a 90 ms one every
     third call), while pageable copies of the same data never did."""
-    import numpy as np
     t = torch.as_tensor(np.ascontiguousarray(array))
     if getattr(device, "type", "cpu") != "cuda":
         return t
     main = torch.cuda.current_stream(device)
-    side = _SIDE_STREAMS.get(device.index)
-    if side is None:
-        side = _SIDE_STREAMS[device.index] = torch.cuda.Stream(device)
+    side = _side_stream(device.index, device)
     with torch.cuda.stream(side):
         d = t.to(device)
     done = torch.cuda.Event()
@@ -94,7 +119,6 @@ def kernel_clock_enable(on=True):
 
 def kernel_clock_read(kernel):
     """(launches, total_ms) of the clocked kernel since the last read; waits for the recorded launches."""
-    import ctypes
     n, ms = ctypes.c_int64(0), ctypes.c_double(0.0)
     _lib.check(_lib.load().am_kernel_clock_read(int(kernel), ctypes.byref(n), ctypes.byref(ms)), "am_kernel_clock_read")
     return n.value, ms.value
@@ -125,7 +149,6 @@ def filter_stats_read(device):
     buf.zero_()
     out = dict(zip(FILTER_STATS_NAMES, values))
     # slot 9 holds the bit pattern of a float: the largest measured |f16 value - exact value| / (fast_c (|x|^2 + G))
-    import struct
     out["bound_ratio_max"] = struct.unpack("<f", struct.pack("<I", int(out["bound_ratio_max"]) & 0xffffffff))[0]
     return out
 
@@ -148,6 +171,32 @@ def _call(lib, name, device, *args):
         else:
             status = getattr(lib, name)(*args)
     _lib.check(status, name)
+
+
+def _run(name, dev, query, query_args, *args):
+    """Entry point `name` with its workspace: the size is what the host query `query` answers for `query_args`, and the
+    workspace pointer and that size are the last two C arguments before the stream.  Returns the workspace (the calls that
+    leave a flag word at its head read it back)."""
+    lib = _lib.load()
+    nb = getattr(lib, query)(*query_args)
+    ws = _workspace(nb, dev)
+    _call(lib, name, dev, *args, _ptr(ws), nb)
+    return ws
+
+
+def _query(stem, f64):
+    """The name of the workspace query of the float64 (am_<stem>_f64_workspace_bytes) or float32 form of an entry point."""
+    return f"am_{stem}_f64_workspace_bytes" if f64 else f"am_{stem}_workspace_bytes"
+
+
+_HOST_CAPS = {}
+
+
+def _host_cap(entry):
+    """The answer of a host query without arguments (a compile-time limit of the library), asked once."""
+    if entry not in _HOST_CAPS:
+        _HOST_CAPS[entry] = int(getattr(_lib.load(), entry)())
+    return _HOST_CAPS[entry]
 
 
 def _require_cuda(t, name):
@@ -217,11 +266,83 @@ def _ld(e):
     return (e.shape[1] + 3) // 4 * 4
 
 
+def _rows(e, name, f64):
+    """(the matrix form the float64 / float32 entry points take, its leading dimension, their suffix "f64" / "f32")"""
+    if f64:
+        e = as_matrix64(e, name)
+        return e, _ld64(e), "f64"
+    e = as_matrix(e, name)
+    return e, _ld(e), "f32"
+
+
+def _any_f64(*sets):
+    """The promotion rule of the reference's numpy code: float64 rows on either side make every set float64."""
+    return any(is_f64(t) for t in sets)
+
+
+def _both_f64(what, *sets):
+    """The rule of the Kernel Audio Distance calls: True when every set holds float64 rows (the *_f64 entry points), False
+    when none does; a mixed pair is refused before anything touches the tensors."""
+    wide = [is_f64(t) for t in sets]
+    if any(wide) and not all(wide):
+        raise NotImplementedError(f"{what} takes float32 rows, or float64 rows in BOTH sets (a mixed pair is not implemented: "
+                                  "convert one side)")
+    return all(wide)
+
+
 def _f64(t, name):
     _require_cuda(t, name)
     if t.dtype != torch.float64 or not t.is_contiguous():
         t = t.to(torch.float64).contiguous()
     return t
+
+
+# ------------------------------------------------------------------ two sets of float32 rows
+def _refuse_f64(op, *tensors):
+    if any(is_f64(t) for t in tensors):
+        raise NotImplementedError(f"{op} takes float32 rows (the float64 matrix-core form is not implemented)")
+
+
+def _check_two_sets(op, x, y, both="x and y", sides=True):
+    """The shape checks of the row-sweep ops: both sets 2-D (`both` names them), of one width and - sides=False: the op words
+    that itself - with rows on both sides."""
+    if x.dim() != 2 or y.dim() != 2:
+        raise ValueError(f"{both} must be 2-D, got shapes {tuple(x.shape)} and {tuple(y.shape)}")
+    if x.shape[1] != y.shape[1]:
+        raise ValueError(f"feature widths differ: {x.shape[1]} and {y.shape[1]}")
+    if sides and (x.shape[0] < 1 or y.shape[0] < 1 or x.shape[1] < 1):
+        raise ValueError(f"{op} needs rows on both sides (got shapes {tuple(x.shape)} and {tuple(y.shape)})")
+
+
+def _two_sets(x, y, names=("x", "y"), more=()):
+    """(x, y, device, n, m, d) of two checked sets in the form the kernels take - prepared once when `x is y` - on one device
+    with the (tensor, name) pairs of `more`, the vectors that go with them."""
+    same = x is y
+    x = as_matrix(x, names[0])
+    y = x if same else as_matrix(y, names[1])
+    for t, name in more:
+        _require_cuda(t, name)
+    dev = _same_device(x, y, *(t for t, _ in more))
+    return x, y, dev, x.shape[0], y.shape[0], x.shape[1]
+
+
+def _check_gram_rows(op, x, y, widths=True):
+    """The row checks of the float32 Gram ops: no float64 side (named), both 2-D tensors and - widths=True - of one width."""
+    for t, name in ((x, "x"), (y, "y")):
+        if is_f64(t):
+            raise NotImplementedError(f"{op} takes float32 rows ({name} holds float64 rows; the float64 matrix-core "
+                                      "form is not implemented)")
+        if not torch.is_tensor(t) or t.dim() != 2:
+            raise ValueError(f"{name} must be a 2-D tensor, got {tuple(getattr(t, 'shape', ()))}")
+    if widths and x.shape[1] != y.shape[1]:
+        raise ValueError(f"feature widths differ: {x.shape[1]} and {y.shape[1]}")
+
+
+def _blocks_mask(blocks):
+    blocks = int(blocks)
+    if blocks < 1 or blocks > 7:
+        raise ValueError(f"blocks={blocks} is not a mask of MMD_XX | MMD_YY | MMD_XY")
+    return blocks
 
 
 # ------------------------------------------------------------------ row groups: rows[idx[offsets[b]:offsets[b + 1]]]
@@ -282,37 +403,27 @@ def _bandwidth_args(bw2, gamma):
 
 
 # ------------------------------------------------------------------ statistics
-def stats(e):
-    """mean f64[D], unbiased covariance f64[D, D] of the rows of e (data.py:37-58), computed in the dtype of e."""
-    if is_f64(e):
-        return stats_f64(e)
-    lib = _lib.load()
-    e = as_matrix(e)
+def _stats(e, f64):
+    e, ld, kind = _rows(e, "embeddings", f64)
     n, d = e.shape
     mean = torch.empty(d, dtype=torch.float64, device=e.device)
     cov = torch.empty((d, d), dtype=torch.float64, device=e.device)
-    nb = lib.am_stats_workspace_bytes(n, d)
-    ws = _workspace(nb, e.device)
-    _call(lib, "am_stats_f32", e.device, _ptr(e), n, d, _ld(e), _ptr(mean), _ptr(cov), _ptr(ws), nb)
+    _run("am_stats_" + kind, e.device, _query("stats", f64), (n, d), _ptr(e), n, d, ld, _ptr(mean), _ptr(cov))
     return mean, cov
+
+
+def stats(e):
+    """mean f64[D], unbiased covariance f64[D, D] of the rows of e (data.py:37-58), computed in the dtype of e."""
+    return stats_f64(e) if is_f64(e) else _stats(e, False)
 
 
 def stats_f64(e):
     """mean f64[D], unbiased covariance f64[D, D] of the rows of a FLOAT64 device matrix, every step in f64 (am_stats_f64):
     the reference computes in the dtype it is given (data.py:39-44)."""
-    lib = _lib.load()
     _require_cuda(e, "embeddings")
     if e.dim() != 2 or e.dtype != torch.float64:
         raise ValueError(f"stats_f64 takes a 2-D float64 matrix, got {tuple(e.shape)} {e.dtype}")
-    if e.stride(1) != 1 or (e.shape[0] > 1 and e.stride(0) < e.shape[1]):
-        e = e.contiguous()
-    n, d = e.shape
-    mean = torch.empty(d, dtype=torch.float64, device=e.device)
-    cov = torch.empty((d, d), dtype=torch.float64, device=e.device)
-    nb = lib.am_stats_f64_workspace_bytes(n, d)
-    ws = _workspace(nb, e.device)
-    _call(lib, "am_stats_f64", e.device, _ptr(e), n, d, e.stride(0) if n > 1 else d, _ptr(mean), _ptr(cov), _ptr(ws), nb)
-    return mean, cov
+    return _stats(e, True)
 
 
 def stats_gather(x, idx, offsets, defer_check=False):
@@ -322,9 +433,7 @@ def stats_gather(x, idx, offsets, defer_check=False):
     ValueError - the kernels never dereference it, they leave its position in the workspace's flag word.
     defer_check=True returns (means, covs, check) without waiting for the device; the caller runs check() - the one host
     read of the flag word - once it has queued the work that consumes the statistics."""
-    lib = _lib.load()
-    f64 = is_f64(x)
-    x = as_matrix64(x) if f64 else as_matrix(x)
+    x, ld, kind = _rows(x, "embeddings", is_f64(x))
     _require_cuda(idx, "idx")
     n, d = x.shape
     offs, b, host_offs = _group_offsets(offsets)
@@ -332,10 +441,8 @@ def stats_gather(x, idx, offsets, defer_check=False):
     dev = x.device
     means = torch.empty((b, d), dtype=torch.float64, device=dev)
     covs = torch.empty((b, d, d), dtype=torch.float64, device=dev)
-    nb = lib.am_stats_gather_workspace_bytes(offs[-1], b, d)
-    ws = _workspace(nb, dev)
-    _call(lib, "am_stats_gather_f64" if f64 else "am_stats_gather_f32", dev, _ptr(x), n, _ld64(x) if f64 else _ld(x), d, _ptr(idx),
-          ctypes.cast(host_offs, ctypes.c_void_p), b, _ptr(means), _ptr(covs), _ptr(ws), nb)
+    ws = _run("am_stats_gather_" + kind, dev, "am_stats_gather_workspace_bytes", (offs[-1], b, d), _ptr(x), n, ld, d, _ptr(idx),
+              _host(host_offs), b, _ptr(means), _ptr(covs))
     check = _index_check(ws, idx, n, "subset rows")
     if defer_check:
         return means, covs, check
@@ -344,42 +451,22 @@ def stats_gather(x, idx, offsets, defer_check=False):
 
 
 def colsum(e):
-    lib = _lib.load()
-    if is_f64(e):
-        e = as_matrix64(e)
-        n, d = e.shape
-        out = torch.empty(d, dtype=torch.float64, device=e.device)
-        nb = lib.am_stats_f64_workspace_bytes(n, d)
-        ws = _workspace(nb, e.device)
-        _call(lib, "am_colsum_f64", e.device, _ptr(e), n, d, _ld64(e), _ptr(out), _ptr(ws), nb)
-        return out
-    e = as_matrix(e)
+    f64 = is_f64(e)
+    e, ld, kind = _rows(e, "embeddings", f64)
     n, d = e.shape
     out = torch.empty(d, dtype=torch.float64, device=e.device)
-    nb = lib.am_stats_workspace_bytes(n, d)
-    ws = _workspace(nb, e.device)
-    _call(lib, "am_colsum_f32", e.device, _ptr(e), n, d, _ld(e), _ptr(out), _ptr(ws), nb)
+    _run("am_colsum_" + kind, e.device, _query("stats", f64), (n, d), _ptr(e), n, d, ld, _ptr(out))
     return out
 
 
 def scatter(e, mean):
     """sum_n (x_n - mean)(x_n - mean)^T, not divided (multi-GPU building block)."""
-    lib = _lib.load()
     mean = _f64(mean, "mean")
-    if is_f64(e):
-        e = as_matrix64(e)
-        n, d = e.shape
-        out = torch.empty((d, d), dtype=torch.float64, device=e.device)
-        nb = lib.am_stats_f64_workspace_bytes(n, d)
-        ws = _workspace(nb, e.device)
-        _call(lib, "am_scatter_f64", e.device, _ptr(e), n, d, _ld64(e), _ptr(mean), _ptr(out), _ptr(ws), nb)
-        return out
-    e = as_matrix(e)
+    f64 = is_f64(e)
+    e, ld, kind = _rows(e, "embeddings", f64)
     n, d = e.shape
     out = torch.empty((d, d), dtype=torch.float64, device=e.device)
-    nb = lib.am_stats_workspace_bytes(n, d)
-    ws = _workspace(nb, e.device)
-    _call(lib, "am_scatter_f32", e.device, _ptr(e), n, d, _ld(e), _ptr(mean), _ptr(out), _ptr(ws), nb)
+    _run("am_scatter_" + kind, e.device, _query("stats", f64), (n, d), _ptr(e), n, d, ld, _ptr(mean), _ptr(out))
     return out
 
 
@@ -400,14 +487,8 @@ def stats_merge(n1, mean1, cov1, n2, mean2, cov2, inplace=False):
     return om, oc
 
 
-_PUSH_MAX = None
-
-
 def stats_push_max_rows():
-    global _PUSH_MAX
-    if _PUSH_MAX is None:
-        _PUSH_MAX = int(_lib.load().am_stats_push_max_rows())
-    return _PUSH_MAX
+    return _host_cap("am_stats_push_max_rows")
 
 
 def stats_push(e, n_old, mean_in, mean_out, cov, rows_out=None, ld_out=0):
@@ -429,23 +510,20 @@ def stats_push(e, n_old, mean_in, mean_out, cov, rows_out=None, ld_out=0):
 # ------------------------------------------------------------------ PCA projection support
 def eigh_descending(a, max_sweeps=40):
     """(eigenvalues f64[D] descending, eigenvectors f64[D, D] with row i = vector i) of a symmetric PSD matrix."""
-    lib = _lib.load()
     a = _f64(a, "matrix")
     d = a.shape[0]
     if a.dim() != 2 or a.shape[1] != d:
         raise ValueError(f"expected a square matrix, got {tuple(a.shape)}")
     evals = torch.empty(d, dtype=torch.float64, device=a.device)
     evecs = torch.empty((d, d), dtype=torch.float64, device=a.device)
-    nb = lib.am_eigh_workspace_bytes(d)
-    ws = _workspace(nb, a.device)
-    _call(lib, "am_eigh_sym_f64", a.device, _ptr(a), d, _ptr(evals), _ptr(evecs), int(max_sweeps), _ptr(ws), nb)
+    _run("am_eigh_sym_f64", a.device, "am_eigh_workspace_bytes", (d,), _ptr(a), d, _ptr(evals), _ptr(evecs), int(max_sweeps))
     return evals, evecs
 
 
 def project(x, mean, components):
     """(x - mean) @ components.T as f64 [N, p] (IncrementalPCA.transform)."""
     lib = _lib.load()
-    x = as_rows(x)
+    x, ld, kind = _rows(x, "embeddings", is_f64(x))
     mean, components = _f64(mean, "mean"), _f64(components, "components")
     n, d = x.shape
     p = components.shape[0]
@@ -453,27 +531,28 @@ def project(x, mean, components):
         raise ValueError(f"projection shapes do not match: x {tuple(x.shape)}, mean {tuple(mean.shape)}, components {tuple(components.shape)}")
     _same_device(x, mean, components)
     out = torch.empty((n, p), dtype=torch.float64, device=x.device)
-    if n > 0 and is_f64(x):
-        _call(lib, "am_project_rows_f64", x.device, _ptr(x), n, _ld64(x), d, _ptr(mean), _ptr(components), p, _ptr(out))
-    elif n > 0:
-        _call(lib, "am_project_f64", x.device, _ptr(x), n, _ld(x), d, _ptr(mean), _ptr(components), p, _ptr(out))
+    if n > 0:
+        _call(lib, "am_project_rows_f64" if kind == "f64" else "am_project_f64", x.device, _ptr(x), n, ld, d, _ptr(mean),
+              _ptr(components), p, _ptr(out))
     return out
 
 
 # ------------------------------------------------------------------ Frechet
-def frechet(mu_x, cov_x, mu_y, cov_y, max_iter=64, tol=1e-13):
-    lib = _lib.load()
+def _frechet_stats(mu_x, cov_x, mu_y, cov_y):
+    """The statistics of frechet / frechet_maps as contiguous f64 device tensors of one D, then D and their device."""
     mu_x, cov_x, mu_y, cov_y = (_f64(t, "stats") for t in (mu_x, cov_x, mu_y, cov_y))
     d = mu_x.numel()
     if cov_x.shape != (d, d) or cov_y.shape != (d, d) or mu_y.numel() != d:
         raise ValueError(f"inconsistent shapes: mu {tuple(mu_x.shape)}/{tuple(mu_y.shape)}, "
                          f"cov {tuple(cov_x.shape)}/{tuple(cov_y.shape)}")
-    _same_device(mu_x, cov_x, mu_y, cov_y)
+    return mu_x, cov_x, mu_y, cov_y, d, _same_device(mu_x, cov_x, mu_y, cov_y)
+
+
+def frechet(mu_x, cov_x, mu_y, cov_y, max_iter=64, tol=1e-13):
+    mu_x, cov_x, mu_y, cov_y, d, dev = _frechet_stats(mu_x, cov_x, mu_y, cov_y)
     out = (ctypes.c_double * 4)()
-    nb = lib.am_frechet_workspace_bytes(d)
-    ws = _workspace(nb, mu_x.device)
-    _call(lib, "am_frechet_f64", mu_x.device, _ptr(mu_x), _ptr(cov_x), _ptr(mu_y), _ptr(cov_y), d, int(max_iter), float(tol),
-                                  ctypes.cast(out, ctypes.c_void_p), _ptr(ws), nb)
+    _run("am_frechet_f64", dev, "am_frechet_workspace_bytes", (d,), _ptr(mu_x), _ptr(cov_x), _ptr(mu_y), _ptr(cov_y), d,
+         int(max_iter), float(tol), _host(out))
     return dict(fd=out[0], tr_sqrt=out[1], iters=int(out[2]), resid=out[3])
 
 
@@ -481,20 +560,12 @@ def frechet_maps(mu_x, cov_x, mu_y, cov_y, max_iter=64, tol=1e-13):
     """frechet() plus the Gaussian optimal-transport maps (am_frechet_maps_f64): the dict of frechet() - the same bits -
     with "stop" (the solver's stop code; 1 = converged), "map_xy" (the symmetric A with A cov_x A = cov_y) and "map_yx" (its
     inverse), both f64 device [D, D], exactly symmetric, and all NaN unless stop == 1."""
-    lib = _lib.load()
-    mu_x, cov_x, mu_y, cov_y = (_f64(t, "stats") for t in (mu_x, cov_x, mu_y, cov_y))
-    d = mu_x.numel()
-    if cov_x.shape != (d, d) or cov_y.shape != (d, d) or mu_y.numel() != d:
-        raise ValueError(f"inconsistent shapes: mu {tuple(mu_x.shape)}/{tuple(mu_y.shape)}, "
-                         f"cov {tuple(cov_x.shape)}/{tuple(cov_y.shape)}")
-    dev = _same_device(mu_x, cov_x, mu_y, cov_y)
+    mu_x, cov_x, mu_y, cov_y, d, dev = _frechet_stats(mu_x, cov_x, mu_y, cov_y)
     out = (ctypes.c_double * 5)()
     map_xy = torch.empty((d, d), dtype=torch.float64, device=dev)
     map_yx = torch.empty((d, d), dtype=torch.float64, device=dev)
-    nb = lib.am_frechet_maps_workspace_bytes(d)
-    ws = _workspace(nb, dev)
-    _call(lib, "am_frechet_maps_f64", dev, _ptr(mu_x), _ptr(cov_x), _ptr(mu_y), _ptr(cov_y), d, int(max_iter), float(tol),
-          ctypes.cast(out, ctypes.c_void_p), _ptr(map_xy), _ptr(map_yx), _ptr(ws), nb)
+    _run("am_frechet_maps_f64", dev, "am_frechet_maps_workspace_bytes", (d,), _ptr(mu_x), _ptr(cov_x), _ptr(mu_y), _ptr(cov_y), d,
+         int(max_iter), float(tol), _host(out), _ptr(map_xy), _ptr(map_yx))
     return dict(fd=out[0], tr_sqrt=out[1], iters=int(out[2]), resid=out[3], stop=int(out[4]), map_xy=map_xy, map_yx=map_yx)
 
 
@@ -503,9 +574,7 @@ def frechet_influence(rows, mu, b, lin, c0):
     all arithmetic in f64, the same bits for float32 rows and their float64 copies).  mu, lin: f64 device [D]; b: f64 device
     [D, D], symmetric; c0: a number.  Returns (psi f64 [N], sums f64 [4] = {sum psi, sum psi^2, finite rows, non-finite
     rows}), both on the device; a row with a non-finite element has psi = NaN and is left out of the sums."""
-    lib = _lib.load()
-    rows = as_rows(rows, "rows")
-    f64 = is_f64(rows)
+    rows, ld, kind = _rows(rows, "rows", is_f64(rows))
     n, d = rows.shape
     mu, b, lin = (_f64(t, "influence terms") for t in (mu, b, lin))
     if n < 1 or mu.numel() != d or lin.numel() != d or tuple(b.shape) != (d, d):
@@ -513,10 +582,8 @@ def frechet_influence(rows, mu, b, lin, c0):
     dev = _same_device(rows, mu, b, lin)
     psi = torch.empty(n, dtype=torch.float64, device=dev)
     sums = torch.empty(4, dtype=torch.float64, device=dev)
-    nb = lib.am_frechet_influence_workspace_bytes(n)
-    ws = _workspace(nb, dev)
-    _call(lib, "am_frechet_influence_f64" if f64 else "am_frechet_influence_f32", dev, _ptr(rows), n, _ld64(rows) if f64 else _ld(rows),
-          d, _ptr(mu), _ptr(b), _ptr(lin), float(c0), _ptr(psi), _ptr(sums), _ptr(ws), nb)
+    _run("am_frechet_influence_" + kind, dev, "am_frechet_influence_workspace_bytes", (n,), _ptr(rows), n, ld, d, _ptr(mu), _ptr(b),
+         _ptr(lin), float(c0), _ptr(psi), _ptr(sums))
     return psi, sums
 
 
@@ -531,9 +598,7 @@ def logit_pass(rows, fold, label, coef, want_z=True):
     sum r, sum loss} over each model's training rows, z f64 [N] - the logit of every row under the model of its own fold,
     NaN where it has none - or None with want_z=False, counts f64 [2] = {rows that took part, rows with a non-finite
     element}), all on the device, stream-ordered, nothing waits for the device.  Two calls return the same bits."""
-    lib = _lib.load()
-    rows = as_rows(rows, "rows")
-    f64 = is_f64(rows)
+    rows, ld, kind = _rows(rows, "rows", is_f64(rows))
     n, d = rows.shape
     coef = _f64(coef, "coef")
     _require_cuda(fold, "fold")
@@ -549,10 +614,8 @@ def logit_pass(rows, fold, label, coef, want_z=True):
     sums = torch.empty((k, d + 2), dtype=torch.float64, device=dev)
     z = torch.empty(n, dtype=torch.float64, device=dev) if want_z else None
     counts = torch.empty(2, dtype=torch.float64, device=dev)
-    nb = lib.am_logit_pass_workspace_bytes(n, d, k)
-    ws = _workspace(nb, dev)
-    _call(lib, "am_logit_pass_f64" if f64 else "am_logit_pass_f32", dev, _ptr(rows), n, _ld64(rows) if f64 else _ld(rows), d, _ptr(fold),
-          int(label), _ptr(coef), k, _ptr(sums), _ptr(z) if want_z else ctypes.c_void_p(None), _ptr(counts), _ptr(ws), nb)
+    _run("am_logit_pass_" + kind, dev, "am_logit_pass_workspace_bytes", (n, d, k), _ptr(rows), n, ld, d, _ptr(fold), int(label),
+         _ptr(coef), k, _ptr(sums), _opt(z), _ptr(counts))
     return sums, z, counts
 
 
@@ -581,12 +644,10 @@ def frechet_batch(mu_x, cov_x, mu_y, cov_y, max_iter=64, tol=1e-13, out=None):
     failure = None
     for s0 in range(0, b, chunk):
         s1 = min(b, s0 + chunk)
-        nb = lib.am_frechet_batch_workspace_bytes(s1 - s0, d)
-        ws = _workspace(nb, dev)
         try:
-            _call(lib, "am_frechet_batch_f64", dev, _ptr(mu_x[s0:s1]), _ptr(cov_x[s0:s1]), _ptr(mu_y if shared else mu_y[s0:s1]),
-                  _ptr(cov_y if shared else cov_y[s0:s1]), 0 if shared else 1, s1 - s0, d, int(max_iter), float(tol), _ptr(out[s0:s1]),
-                  _ptr(ws), nb)
+            _run("am_frechet_batch_f64", dev, "am_frechet_batch_workspace_bytes", (s1 - s0, d), _ptr(mu_x[s0:s1]), _ptr(cov_x[s0:s1]),
+                 _ptr(mu_y if shared else mu_y[s0:s1]), _ptr(cov_y if shared else cov_y[s0:s1]), 0 if shared else 1, s1 - s0, d,
+                 int(max_iter), float(tol), _ptr(out[s0:s1]))
         except _lib.HipLibraryError as e:                     # (a stop code 4 in this chunk; the other chunks still run)
             failure = failure or e
     rec = out.cpu().tolist()                                  # one device -> host copy of B x 5 doubles
@@ -599,14 +660,8 @@ def frechet_batch(mu_x, cov_x, mu_y, cov_y, max_iter=64, tol=1e-13, out=None):
     return [dict(fd=r[0], tr_sqrt=r[1], iters=int(r[2]), resid=r[3], stop=int(r[4])) for r in rec]
 
 
-_GROUPS_MAX = None
-
-
 def frechet_groups_max_rows():
-    global _GROUPS_MAX
-    if _GROUPS_MAX is None:
-        _GROUPS_MAX = int(_lib.load().am_frechet_groups_max_rows())
-    return _GROUPS_MAX
+    return _host_cap("am_frechet_groups_max_rows")
 
 
 def frechet_groups(rows, idx, offsets, mu_y, cov_y, out=None):
@@ -616,9 +671,7 @@ def frechet_groups(rows, idx, offsets, mu_y, cov_y, out=None):
     reference (mu_y [D], cov_y [D, D]).  Nothing waits for the device: returns (out, check) with out the f64 device tensor
     [B, 5] of { fd, tr_sqrt, sweeps, residual, stop code } records and check() the one host read of the workspace's flag
     word, which raises ValueError for an index outside [0, N) (the kernels never dereference it)."""
-    lib = _lib.load()
-    f64 = is_f64(rows)
-    rows = as_rows(rows)
+    rows, ld, kind = _rows(rows, "embeddings", is_f64(rows))
     n, d = rows.shape
     mu_y, cov_y = _f64(mu_y, "mu_y"), _f64(cov_y, "cov_y")
     if mu_y.numel() != d or tuple(cov_y.shape) != (d, d):
@@ -627,29 +680,21 @@ def frechet_groups(rows, idx, offsets, mu_y, cov_y, out=None):
     dev = _same_device(rows, mu_y, cov_y)
     idx = _group_index(idx, offs[-1], rows)
     out = _records_out(out, b, dev, "rows'")
-    nb = lib.am_frechet_groups_workspace_bytes(offs[-1], b, d)
-    ws = _workspace(nb, dev)
-    _call(lib, "am_frechet_groups_f64" if f64 else "am_frechet_groups_f32", dev, _ptr(rows), n, _ld64(rows) if f64 else _ld(rows), d,
-          _ptr(idx) if idx is not None else ctypes.c_void_p(None), ctypes.cast(host_offs, ctypes.c_void_p), b, _ptr(mu_y), _ptr(cov_y),
-          _ptr(out), _ptr(ws), nb)
+    ws = _run("am_frechet_groups_" + kind, dev, "am_frechet_groups_workspace_bytes", (offs[-1], b, d), _ptr(rows), n, ld, d, _opt(idx),
+              _host(host_offs), b, _ptr(mu_y), _ptr(cov_y), _ptr(out))
     return out, _index_check(ws, idx, n, "group rows")
 
 
 # ------------------------------------------------------------------ Vendi score
 VENDI_KERNELS = {"cosine": 0, "gaussian": 1}                 # enum am_vendi_kernel
-_VENDI_CAPS = {}
 
 
 def vendi_groups_max_rows():
-    if "groups" not in _VENDI_CAPS:
-        _VENDI_CAPS["groups"] = int(_lib.load().am_vendi_groups_max_rows())
-    return _VENDI_CAPS["groups"]
+    return _host_cap("am_vendi_groups_max_rows")
 
 
 def vendi_gram_max_rows():
-    if "gram" not in _VENDI_CAPS:
-        _VENDI_CAPS["gram"] = int(_lib.load().am_vendi_gram_max_rows())
-    return _VENDI_CAPS["gram"]
+    return _host_cap("am_vendi_gram_max_rows")
 
 
 def _vendi_kernel_args(kernel, gamma, gamma_dev):
@@ -692,9 +737,7 @@ def vendi_groups(rows, idx, offsets, kernel="cosine", gamma=None, gamma_dev=None
     index outside [0, N)."""
     code, gamma_arg, dev_arg = _vendi_kernel_args(kernel, gamma, gamma_dev)
     offs, b, host_offs = _group_offsets(offsets)
-    lib = _lib.load()
-    f64 = is_f64(rows)
-    rows = as_rows(rows)
+    rows, ld, kind = _rows(rows, "embeddings", is_f64(rows))
     n, d = rows.shape
     dev = rows.device
     if gamma_dev is not None:
@@ -702,11 +745,8 @@ def vendi_groups(rows, idx, offsets, kernel="cosine", gamma=None, gamma_dev=None
     idx = _group_index(idx, offs[-1], rows)
     rec = torch.empty((b, 8), dtype=torch.float64, device=dev)
     evals = torch.empty(offs[-1], dtype=torch.float64, device=dev)
-    nb = lib.am_vendi_groups_workspace_bytes(offs[-1], b, d)
-    ws = _workspace(nb, dev)
-    _call(lib, "am_vendi_groups_f64" if f64 else "am_vendi_groups_f32", dev, _ptr(rows), n, _ld64(rows) if f64 else _ld(rows), d,
-          _ptr(idx) if idx is not None else ctypes.c_void_p(None), ctypes.cast(host_offs, ctypes.c_void_p), b, code, gamma_arg, dev_arg,
-          _ptr(rec), _ptr(evals), _ptr(ws), nb)
+    ws = _run("am_vendi_groups_" + kind, dev, "am_vendi_groups_workspace_bytes", (offs[-1], b, d), _ptr(rows), n, ld, d, _opt(idx),
+              _host(host_offs), b, code, gamma_arg, dev_arg, _ptr(rec), _ptr(evals))
     return rec, evals, _index_check(ws, idx, n, "group rows")
 
 
@@ -719,19 +759,15 @@ def vendi_gram(rows, idx=None, kernel="cosine", gamma=None, gamma_dev=None):
     n_rows = int(rows.shape[0]) if idx is None else int(idx.numel())
     if not 1 <= n_rows <= vendi_gram_max_rows():
         raise ValueError(f"vendi_gram takes 1 .. {vendi_gram_max_rows()} rows, got {n_rows}")
-    lib = _lib.load()
-    f64 = is_f64(rows)
-    rows = as_rows(rows)
+    rows, ld, kind = _rows(rows, "embeddings", is_f64(rows))
     n, d = rows.shape
     dev = rows.device
     if gamma_dev is not None:
         _same_device(rows, gamma_dev)
     idx = _group_index(idx, n_rows, rows)
     m = torch.empty((n_rows, n_rows), dtype=torch.float64, device=dev)
-    nb = lib.am_vendi_gram_workspace_bytes(n_rows, d)
-    ws = _workspace(nb, dev)
-    _call(lib, "am_vendi_gram_f64" if f64 else "am_vendi_gram_f32", dev, _ptr(rows), n, _ld64(rows) if f64 else _ld(rows), d,
-          _ptr(idx) if idx is not None else ctypes.c_void_p(None), n_rows, code, gamma_arg, dev_arg, _ptr(m), _ptr(ws), nb)
+    ws = _run("am_vendi_gram_" + kind, dev, "am_vendi_gram_workspace_bytes", (n_rows, d), _ptr(rows), n, ld, d, _opt(idx), n_rows, code,
+              gamma_arg, dev_arg, _ptr(m))
     return m, _whole_set_check(ws, idx, n, "rows")
 
 
@@ -745,16 +781,10 @@ def vendi_moment(rows):
     dual form of the cosine kernel's K / n, with the same non-zero eigenvalues.  Returns (s, check) as vendi_gram does."""
     if rows.dim() != 2 or rows.shape[0] < 1:
         raise ValueError(f"vendi_moment takes a non-empty 2-D matrix of rows, got shape {tuple(rows.shape)}")
-    lib = _lib.load()
-    f64 = is_f64(rows)
-    rows = as_rows(rows)
+    rows, ld, kind = _rows(rows, "embeddings", is_f64(rows))
     n, d = rows.shape
-    dev = rows.device
-    s = torch.empty((d, d), dtype=torch.float64, device=dev)
-    nb = lib.am_vendi_moment_workspace_bytes(n, d)
-    ws = _workspace(nb, dev)
-    _call(lib, "am_vendi_moment_f64" if f64 else "am_vendi_moment_f32", dev, _ptr(rows), n, _ld64(rows) if f64 else _ld(rows), d, _ptr(s),
-          _ptr(ws), nb)
+    s = torch.empty((d, d), dtype=torch.float64, device=rows.device)
+    ws = _run("am_vendi_moment_" + kind, rows.device, "am_vendi_moment_workspace_bytes", (n, d), _ptr(rows), n, ld, d, _ptr(s))
     return s, _whole_set_check(ws, None, n, "rows")
 
 
@@ -769,9 +799,7 @@ class FrechetJob:
         self._d = stats[0].numel()
         self._nb = lib.am_frechet_workspace_bytes(self._d)
         main = torch.cuda.current_stream(dev)
-        self._side = _SIDE_STREAMS.get(("fad", dev.index))
-        if self._side is None:
-            self._side = _SIDE_STREAMS[("fad", dev.index)] = torch.cuda.Stream(dev)
+        self._side = _side_stream(("fad", dev.index), dev)
         self._side.wait_stream(main)                         # the statistics were produced on the caller's stream
         with torch.cuda.stream(self._side):
             self._ws = _workspace(self._nb, dev)
@@ -824,46 +852,27 @@ def apa_scalar(d_y_x, d_y_xp, d_x_xp):
 def kd_poly(x, y, idx1, idx2, gamma, coef0, degree):
     """Per-subset unbiased MMD^2 (f64[S] device tensor).  idx1/idx2: int64 [S, m].  float64 features (either side: numpy's
     matmul promotes, kd.py:115) run every product and sum in f64 (am_kd_poly_f64)."""
-    lib = _lib.load()
     idx1, idx2 = _index_table(idx1, "idx1"), _index_table(idx2, "idx2")
     s, m = idx1.shape
-    if is_f64(x) or is_f64(y):
-        x, y = as_matrix64(x, "features_1"), as_matrix64(y, "features_2")
-        out = torch.empty(s, dtype=torch.float64, device=x.device)
-        nb = lib.am_kd_f64_workspace_bytes(s, m)
-        ws = _workspace(nb, x.device)
-        _call(lib, "am_kd_poly_f64", x.device, _ptr(x), x.shape[0], _ld64(x), _ptr(y), y.shape[0], _ld64(y), x.shape[1],
-              _ptr(idx1), _ptr(idx2), s, m, float(gamma), float(coef0), int(degree), _ptr(out), _ptr(ws), nb)
-        return out
-    x, y = as_matrix(x, "features_1"), as_matrix(y, "features_2")
+    f64 = _any_f64(x, y)
+    (x, ldx, kind), (y, ldy, _) = _rows(x, "features_1", f64), _rows(y, "features_2", f64)
+    d = x.shape[1]
     out = torch.empty(s, dtype=torch.float64, device=x.device)
-    nb = lib.am_kd_poly_workspace_bytes(s, m, x.shape[1])
-    ws = _workspace(nb, x.device)
-    _call(lib, "am_kd_poly_f32", x.device, _ptr(x), x.shape[0], _ld(x), _ptr(y), y.shape[0], _ld(y), x.shape[1],
-                                  _ptr(idx1), _ptr(idx2), s, m, float(gamma), float(coef0), int(degree),
-                                  _ptr(out), _ptr(ws), nb)
+    query = ("am_kd_f64_workspace_bytes", (s, m)) if f64 else ("am_kd_poly_workspace_bytes", (s, m, d))
+    _run("am_kd_poly_" + kind, x.device, *query, _ptr(x), x.shape[0], ldx, _ptr(y), y.shape[0], ldy, d, _ptr(idx1), _ptr(idx2), s, m,
+         float(gamma), float(coef0), int(degree), _ptr(out))
     return out
 
 
 def kd_rbf(x, y, idx1, idx2, sigma):
     """Per-subset unbiased MMD^2 with the RBF kernel exp(-|x-y|^2 / (2 sigma^2)) (f64[S] device tensor)."""
-    lib = _lib.load()
     idx1, idx2 = _index_table(idx1, "idx1"), _index_table(idx2, "idx2")
     s, m = idx1.shape
-    if is_f64(x) or is_f64(y):
-        x, y = as_matrix64(x, "features_1"), as_matrix64(y, "features_2")
-        out = torch.empty(s, dtype=torch.float64, device=x.device)
-        nb = lib.am_kd_f64_workspace_bytes(s, m)
-        ws = _workspace(nb, x.device)
-        _call(lib, "am_kd_rbf_f64", x.device, _ptr(x), x.shape[0], _ld64(x), _ptr(y), y.shape[0], _ld64(y), x.shape[1], _ptr(idx1),
-              _ptr(idx2), s, m, float(sigma), _ptr(out), _ptr(ws), nb)
-        return out
-    x, y = as_matrix(x, "features_1"), as_matrix(y, "features_2")
+    f64 = _any_f64(x, y)
+    (x, ldx, kind), (y, ldy, _) = _rows(x, "features_1", f64), _rows(y, "features_2", f64)
     out = torch.empty(s, dtype=torch.float64, device=x.device)
-    nb = lib.am_kd_rbf_workspace_bytes(s, m)
-    ws = _workspace(nb, x.device)
-    _call(lib, "am_kd_rbf_f32", x.device, _ptr(x), x.shape[0], _ld(x), _ptr(y), y.shape[0], _ld(y), x.shape[1], _ptr(idx1), _ptr(idx2),
-          s, m, float(sigma), _ptr(out), _ptr(ws), nb)
+    _run("am_kd_rbf_" + kind, x.device, "am_kd_f64_workspace_bytes" if f64 else "am_kd_rbf_workspace_bytes", (s, m), _ptr(x),
+         x.shape[0], ldx, _ptr(y), y.shape[0], ldy, x.shape[1], _ptr(idx1), _ptr(idx2), s, m, float(sigma), _ptr(out))
     return out
 
 
@@ -871,40 +880,17 @@ def kd_rbf(x, y, idx1, idx2, sigma):
 MMD_XX, MMD_YY, MMD_XY = 1, 2, 4                       # enum am_mmd_block
 
 
-def _kad_kind(what, *sets):
-    """"f64" when every set holds float64 rows (the *_f64 entry points of the Kernel Audio Distance calls), "f32" when none
-    does; a mixed pair is refused before anything touches the tensors."""
-    wide = [is_f64(t) for t in sets]
-    if any(wide) and not all(wide):
-        raise NotImplementedError(f"{what} takes float32 rows, or float64 rows in BOTH sets (a mixed pair is not implemented: "
-                                  "convert one side)")
-    return "f64" if all(wide) else "f32"
-
-
-def _kad_matrix(kind, e, name):
-    """(the matrix form the `kind` entry points take, its leading dimension)"""
-    if kind == "f64":
-        e = as_matrix64(e, name)
-        return e, _ld64(e)
-    e = as_matrix(e, name)
-    return e, _ld(e)
-
-
 def pairwise_select_sq(x, rank=None):
     """The element of 0-based `rank` (None: the lower median, torch.median's convention) among the float32 squared
     distances of the N (N - 1) / 2 unordered row pairs of x, as a 0-dim float32 DEVICE tensor: an exact radix select over
     recomputed Gram tiles (am_pairwise_select_f32; float64 rows: am_pairwise_select_f64, every distance in f64 and the
     result its float32 rounding), stream-ordered, no host synchronisation."""
-    lib = _lib.load()
-    kind = _kad_kind("pairwise_select_sq", x)
-    x, ld = _kad_matrix(kind, x, "x")
+    f64 = _both_f64("pairwise_select_sq", x)
+    x, ld, kind = _rows(x, "x", f64)
     n, d = x.shape
     out = torch.empty((), dtype=torch.float32, device=x.device)
-    query = lib.am_pairwise_select_f64_workspace_bytes if kind == "f64" else lib.am_pairwise_select_workspace_bytes
-    nb = query(n, d)
-    ws = _workspace(nb, x.device)
-    _call(lib, "am_pairwise_select_" + kind, x.device, _ptr(x), n, ld, d, -1 if rank is None else int(rank), _ptr(out),
-          _ptr(ws), nb)
+    _run("am_pairwise_select_" + kind, x.device, _query("pairwise_select", f64), (n, d), _ptr(x), n, ld, d,
+         -1 if rank is None else int(rank), _ptr(out))
     return out
 
 
@@ -914,10 +900,9 @@ def mmd_rbf_sums(x, y, bw2=None, gamma=None, blocks=7, out=None):
     (gamma = 0.5 / bw2 is formed on the device - the output of pairwise_select_sq, no host round trip) or `gamma`: a number.
     Only the slots named by `blocks` (MMD_XX | MMD_YY | MMD_XY) are written; the others keep what `out` held (NaN in a
     fresh tensor)."""
-    lib = _lib.load()
-    kind = _kad_kind("mmd_rbf_sums", x, y)
+    f64 = _both_f64("mmd_rbf_sums", x, y)
     bw2_arg, gamma_arg = _bandwidth_args(bw2, gamma)
-    (x, ldx), (y, ldy) = _kad_matrix(kind, x, "x"), _kad_matrix(kind, y, "y")
+    (x, ldx, kind), (y, ldy, _) = _rows(x, "x", f64), _rows(y, "y", f64)
     dev = _same_device(x, y)
     if x.shape[1] != y.shape[1]:
         raise ValueError(f"feature widths differ: {x.shape[1]} and {y.shape[1]}")
@@ -926,11 +911,8 @@ def mmd_rbf_sums(x, y, bw2=None, gamma=None, blocks=7, out=None):
     elif not (out.is_cuda and out.dtype == torch.float64 and out.numel() == 3 and out.is_contiguous()):
         raise ValueError("out must be a contiguous float64[3] device tensor")
     blocks = int(blocks)
-    query = lib.am_mmd_rbf_f64_workspace_bytes if kind == "f64" else lib.am_mmd_rbf_workspace_bytes
-    nb = query(x.shape[0], y.shape[0], x.shape[1], blocks)
-    ws = _workspace(nb, dev)
-    _call(lib, "am_mmd_rbf_" + kind, dev, _ptr(x), x.shape[0], ldx, _ptr(y), y.shape[0], ldy, x.shape[1],
-          bw2_arg, gamma_arg, blocks, _ptr(out), _ptr(ws), nb)
+    _run("am_mmd_rbf_" + kind, dev, _query("mmd_rbf", f64), (x.shape[0], y.shape[0], x.shape[1], blocks), _ptr(x), x.shape[0], ldx,
+         _ptr(y), y.shape[0], ldy, x.shape[1], bw2_arg, gamma_arg, blocks, _ptr(out))
     return out
 
 
@@ -941,30 +923,17 @@ def mmd_rbf_row_sums(x, y, bw2=None, gamma=None, blocks=7):
     work of mmd_rbf_sums with the same `blocks`.  A side no named block writes is None; a column of a block that is not
     named holds NaN.  `bw2` / `gamma` as for mmd_rbf_sums.  float32 rows only; stream-ordered, nothing waits for the
     device."""
-    for t, name in ((x, "x"), (y, "y")):
-        if is_f64(t):
-            raise NotImplementedError(f"mmd_rbf_row_sums takes float32 rows ({name} holds float64 rows; the float64 matrix-core "
-                                      "form is not implemented)")
-        if not torch.is_tensor(t) or t.dim() != 2:
-            raise ValueError(f"{name} must be a 2-D tensor, got {tuple(getattr(t, 'shape', ()))}")
-    if x.shape[1] != y.shape[1]:
-        raise ValueError(f"feature widths differ: {x.shape[1]} and {y.shape[1]}")
-    blocks = int(blocks)
-    if blocks < 1 or blocks > 7:
-        raise ValueError(f"blocks={blocks} is not a mask of MMD_XX | MMD_YY | MMD_XY")
+    _check_gram_rows("mmd_rbf_row_sums", x, y)
+    blocks = _blocks_mask(blocks)
     bw2_arg, gamma_arg = _bandwidth_args(bw2, gamma)
-    lib = _lib.load()
     x, y = as_matrix(x, "x"), as_matrix(y, "y")
     dev = _same_device(x, y)
     (n, d), m = x.shape, y.shape[0]
     nan = float("nan")
     out_x = torch.full((n, 2), nan, dtype=torch.float64, device=dev) if blocks & (MMD_XX | MMD_XY) else None
     out_y = torch.full((m, 2), nan, dtype=torch.float64, device=dev) if blocks & (MMD_YY | MMD_XY) else None
-    nb = lib.am_mmd_rbf_rows_workspace_bytes(n, m, d, blocks)
-    ws = _workspace(nb, dev)
-    null = ctypes.c_void_p(None)
-    _call(lib, "am_mmd_rbf_rows_f32", dev, _ptr(x), n, _ld(x), _ptr(y), m, _ld(y), d, bw2_arg, gamma_arg, blocks,
-          _ptr(out_x) if out_x is not None else null, _ptr(out_y) if out_y is not None else null, _ptr(ws), nb)
+    _run("am_mmd_rbf_rows_f32", dev, "am_mmd_rbf_rows_workspace_bytes", (n, m, d, blocks), _ptr(x), n, _ld(x), _ptr(y), m, _ld(y), d,
+         bw2_arg, gamma_arg, blocks, _opt(out_x), _opt(out_y))
     return out_x, out_y
 
 
@@ -993,17 +962,8 @@ def mmd_rbf_cell_sums(x, y, idx_x=None, idx_y=None, units_x=None, units_y=None, 
     of the two units, inside one set without p == q (by position).  `bw2` / `gamma` as for mmd_rbf_sums.  float32 rows only.
     Where an index list was given the flag word of the call is read back (the one host synchronisation) and an index
     outside [0, n) other than -1 raises ValueError; the kernels never dereference it."""
-    for t, name in ((x, "x"), (y, "y")):
-        if is_f64(t):
-            raise NotImplementedError(f"mmd_rbf_cell_sums takes float32 rows ({name} holds float64 rows; the float64 matrix-core "
-                                      "form is not implemented)")
-        if not torch.is_tensor(t) or t.dim() != 2:
-            raise ValueError(f"{name} must be a 2-D tensor, got {tuple(getattr(t, 'shape', ()))}")
-    if x.shape[1] != y.shape[1]:
-        raise ValueError(f"feature widths differ: {x.shape[1]} and {y.shape[1]}")
-    blocks = int(blocks)
-    if blocks < 1 or blocks > 7:
-        raise ValueError(f"blocks={blocks} is not a mask of MMD_XX | MMD_YY | MMD_XY")
+    _check_gram_rows("mmd_rbf_cell_sums", x, y)
+    blocks = _blocks_mask(blocks)
     bw2_arg, gamma_arg = _bandwidth_args(bw2, gamma)
     pos = []
     for idx, rows, name in ((idx_x, x.shape[0], "idx_x"), (idx_y, y.shape[0], "idx_y")):
@@ -1011,7 +971,6 @@ def mmd_rbf_cell_sums(x, y, idx_x=None, idx_y=None, units_x=None, units_y=None, 
             raise ValueError(f"{name} must be a non-empty 1-D integer tensor of stored-row indices")
         pos.append(int(idx.numel()) if idx is not None else int(rows))
     (u1, host_ux), (u2, host_uy) = _cell_units(units_x, pos[0], "units_x"), _cell_units(units_y, pos[1], "units_y")
-    lib = _lib.load()
     x, y = as_matrix(x, "x"), as_matrix(y, "y")
     dev = _same_device(x, y)
     idx_x, idx_y = _group_index(idx_x, pos[0], x), _group_index(idx_y, pos[1], y)
@@ -1020,14 +979,9 @@ def mmd_rbf_cell_sums(x, y, idx_x=None, idx_y=None, units_x=None, units_y=None, 
     xx = torch.full((u1, u1), nan, dtype=torch.float64, device=dev) if blocks & MMD_XX else None
     yy = torch.full((u2, u2), nan, dtype=torch.float64, device=dev) if blocks & MMD_YY else None
     xy = torch.full((u1, u2), nan, dtype=torch.float64, device=dev) if blocks & MMD_XY else None
-    nb = lib.am_mmd_rbf_cells_workspace_bytes(pos[0], pos[1], d, blocks)
-    ws = _workspace(nb, dev)
-    null = ctypes.c_void_p(None)
-    opt = lambda t: _ptr(t) if t is not None else null
-    host = lambda a: ctypes.cast(a, ctypes.c_void_p) if a is not None else null
-    _call(lib, "am_mmd_rbf_cells_f32", dev, _ptr(x), n, _ld(x), opt(idx_x), pos[0], host(host_ux), u1,
-          _ptr(y), m, _ld(y), opt(idx_y), pos[1], host(host_uy), u2, d, bw2_arg, gamma_arg, blocks, opt(xx), opt(yy), opt(xy),
-          _ptr(ws), nb)
+    ws = _run("am_mmd_rbf_cells_f32", dev, "am_mmd_rbf_cells_workspace_bytes", (pos[0], pos[1], d, blocks), _ptr(x), n, _ld(x),
+              _opt(idx_x), pos[0], _host(host_ux), u1, _ptr(y), m, _ld(y), _opt(idx_y), pos[1], _host(host_uy), u2, d, bw2_arg,
+              gamma_arg, blocks, _opt(xx), _opt(yy), _opt(xy))
     if idx_x is not None or idx_y is not None:
         flag = int(ws[:8].view(torch.int64).item())
         if flag != 0:
@@ -1058,73 +1012,9 @@ def mmd_scales(scales):
     return grid
 
 
-def mmd_multi_sums(x, y, kernel, scales, bw2=None, blocks=7, out=None):
-    """float64 [3, S] device tensor: row 0 Sxx, 1 Syy, 2 Sxy (ordered pairs i != j / all pairs, as mmd_rbf_sums) of S kernels
-    of one family in one Gram pass per at most four scales (am_mmd_multi_f32).  `kernel`: "gaussian" exp(-d2 g),
-    g = 0.5 / (bw2 c c); "laplacian" exp(-d h), h = 1 / (c sqrt(bw2)); "energy" -d (one scale, no bandwidth) - c running over
-    `scales`.  `bw2`: a 0-dim float32 DEVICE tensor (the output of pairwise_select_sq, no host round trip) or a number.  The
-    Gaussian column of scale c holds the bits of mmd_rbf_sums(gamma=0.5 / (bw2 * (c * c))); no column depends on the other
-    scales or on where a longer grid is cut into calls.  Only the rows named by `blocks` are written; the others keep what
-    `out` held (NaN in a fresh tensor).  float32 rows only; stream-ordered, nothing waits for the device."""
-    if kernel not in MMD_KERNELS:
-        raise ValueError(f"kernel={kernel!r} is not one of {sorted(MMD_KERNELS)}")
-    grid = mmd_scales(scales)
-    if kernel == "energy" and len(grid) != 1:
-        raise ValueError(f'the "energy" kernel has no bandwidth: it takes one scale, got {len(grid)}')
-    for t, name in ((x, "x"), (y, "y")):
-        if is_f64(t):
-            raise NotImplementedError(f"mmd_multi_sums takes float32 rows ({name} holds float64 rows; the float64 matrix-core form "
-                                      "is not implemented)")
-        if not torch.is_tensor(t) or t.dim() != 2:
-            raise ValueError(f"{name} must be a 2-D tensor, got {tuple(getattr(t, 'shape', ()))}")
-    if x.shape[1] != y.shape[1]:
-        raise ValueError(f"feature widths differ: {x.shape[1]} and {y.shape[1]}")
-    blocks = int(blocks)
-    if blocks < 1 or blocks > 7:
-        raise ValueError(f"blocks={blocks} is not a mask of MMD_XX | MMD_YY | MMD_XY")
-    bw2_arg, bw2_host = ctypes.c_void_p(None), 0.0
-    if kernel != "energy":
-        if bw2 is None:
-            raise ValueError(f'the "{kernel}" kernel needs bw2 (a float32 device scalar or a number)')
-        if torch.is_tensor(bw2):
-            _require_cuda(bw2, "bw2")
-            if bw2.dtype != torch.float32 or bw2.numel() != 1:
-                raise ValueError("bw2 must be a float32 device scalar")
-            bw2_arg = _ptr(bw2)
-        else:
-            bw2_host = float(bw2)
-            if not (bw2_host > 0.0 and bw2_host < float("inf")):
-                raise ValueError(f"bw2={bw2!r} must be finite and positive")
-    nscales = len(grid)
-    lib = _lib.load()
-    x, y = as_matrix(x, "x"), as_matrix(y, "y")
-    dev = _same_device(x, y)
-    if out is None:
-        out = torch.full((3, nscales), float("nan"), dtype=torch.float64, device=dev)
-    elif not (out.device == dev and out.dtype == torch.float64 and tuple(out.shape) == (3, nscales) and out.is_contiguous()):
-        raise ValueError(f"out must be a contiguous float64 [3, {nscales}] tensor on the device of the rows")
-    (n, d), m = x.shape, y.shape[0]
-    rows = [b for b in range(3) if blocks & (1 << b)]
-    for first in range(0, nscales, MMD_MULTI_MAX):
-        part = grid[first:first + MMD_MULTI_MAX]
-        k = len(part)
-        # the library writes a dense [3][k]: the whole of `out`, or a staging tensor whose named rows go to columns first .. first + k
-        dst = out if k == nscales else torch.empty((3, k), dtype=torch.float64, device=dev)
-        nb = lib.am_mmd_multi_workspace_bytes(n, m, d, k, blocks)
-        ws = _workspace(nb, dev)
-        _call(lib, "am_mmd_multi_f32", dev, _ptr(x), n, _ld(x), _ptr(y), m, _ld(y), d, MMD_KERNELS[kernel], bw2_arg, bw2_host,
-              ctypes.cast((ctypes.c_double * k)(*part), ctypes.c_void_p), k, blocks, _ptr(dst), _ptr(ws), nb)
-        if dst is not out:
-            for b in rows:
-                out[b, first:first + k].copy_(dst[b])
-    return out
-
-
-PAIR_DEPENDENCE_MIN_ROWS = 4                                         # the unbiased statistics divide by n - 3
-
-
 def _side_bandwidth(kernel, bw2, name):
-    """(device pointer, host value) of one side's squared bandwidth for pair_dependence."""
+    """(device pointer, host value) of a squared bandwidth `name` of the `kernel` family: a float32 device scalar or a number;
+    the "energy" kernel has none."""
     if kernel == "energy":
         return ctypes.c_void_p(None), 0.0
     if bw2 is None:
@@ -1140,6 +1030,47 @@ def _side_bandwidth(kernel, bw2, name):
     return ctypes.c_void_p(None), host
 
 
+def mmd_multi_sums(x, y, kernel, scales, bw2=None, blocks=7, out=None):
+    """float64 [3, S] device tensor: row 0 Sxx, 1 Syy, 2 Sxy (ordered pairs i != j / all pairs, as mmd_rbf_sums) of S kernels
+    of one family in one Gram pass per at most four scales (am_mmd_multi_f32).  `kernel`: "gaussian" exp(-d2 g),
+    g = 0.5 / (bw2 c c); "laplacian" exp(-d h), h = 1 / (c sqrt(bw2)); "energy" -d (one scale, no bandwidth) - c running over
+    `scales`.  `bw2`: a 0-dim float32 DEVICE tensor (the output of pairwise_select_sq, no host round trip) or a number.  The
+    Gaussian column of scale c holds the bits of mmd_rbf_sums(gamma=0.5 / (bw2 * (c * c))); no column depends on the other
+    scales or on where a longer grid is cut into calls.  Only the rows named by `blocks` are written; the others keep what
+    `out` held (NaN in a fresh tensor).  float32 rows only; stream-ordered, nothing waits for the device."""
+    if kernel not in MMD_KERNELS:
+        raise ValueError(f"kernel={kernel!r} is not one of {sorted(MMD_KERNELS)}")
+    grid = mmd_scales(scales)
+    if kernel == "energy" and len(grid) != 1:
+        raise ValueError(f'the "energy" kernel has no bandwidth: it takes one scale, got {len(grid)}')
+    _check_gram_rows("mmd_multi_sums", x, y)
+    blocks = _blocks_mask(blocks)
+    bw2_arg, bw2_host = _side_bandwidth(kernel, bw2, "bw2")
+    nscales = len(grid)
+    x, y = as_matrix(x, "x"), as_matrix(y, "y")
+    dev = _same_device(x, y)
+    if out is None:
+        out = torch.full((3, nscales), float("nan"), dtype=torch.float64, device=dev)
+    elif not (out.device == dev and out.dtype == torch.float64 and tuple(out.shape) == (3, nscales) and out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous float64 [3, {nscales}] tensor on the device of the rows")
+    (n, d), m = x.shape, y.shape[0]
+    rows = [b for b in range(3) if blocks & (1 << b)]
+    for first in range(0, nscales, MMD_MULTI_MAX):
+        part = grid[first:first + MMD_MULTI_MAX]
+        k = len(part)
+        # the library writes a dense [3][k]: the whole of `out`, or a staging tensor whose named rows go to columns first .. first + k
+        dst = out if k == nscales else torch.empty((3, k), dtype=torch.float64, device=dev)
+        _run("am_mmd_multi_f32", dev, "am_mmd_multi_workspace_bytes", (n, m, d, k, blocks), _ptr(x), n, _ld(x), _ptr(y), m, _ld(y), d,
+             MMD_KERNELS[kernel], bw2_arg, bw2_host, _host((ctypes.c_double * k)(*part)), k, blocks, _ptr(dst))
+        if dst is not out:
+            for b in rows:
+                out[b, first:first + k].copy_(dst[b])
+    return out
+
+
+PAIR_DEPENDENCE_MIN_ROWS = 4                                         # the unbiased statistics divide by n - 3
+
+
 def pair_dependence(x, y, kernel, bw2x=None, bw2y=None, perm=None):
     """Row sums of the product of two Gram matrices of PAIRED sets in one library call (am_pair_dependence_f32): row i of x
     [n, dx] belongs to row i of y [n, dy] - with `perm` (int64 device tensor [n]) to row perm[i] of y, addressed through the
@@ -1151,12 +1082,7 @@ def pair_dependence(x, y, kernel, bw2x=None, bw2y=None, perm=None):
     host round trip) or a number.  float32 rows only; stream-ordered, nothing waits for the device."""
     if kernel not in MMD_KERNELS:
         raise ValueError(f"kernel={kernel!r} is not one of {sorted(MMD_KERNELS)}")
-    for t, name in ((x, "x"), (y, "y")):
-        if is_f64(t):
-            raise NotImplementedError(f"pair_dependence takes float32 rows ({name} holds float64 rows; the float64 matrix-core "
-                                      "form is not implemented)")
-        if not torch.is_tensor(t) or t.dim() != 2:
-            raise ValueError(f"{name} must be a 2-D tensor, got {tuple(getattr(t, 'shape', ()))}")
+    _check_gram_rows("pair_dependence", x, y, widths=False)
     if x.shape[0] != y.shape[0]:
         raise ValueError(f"row counts differ: {x.shape[0]} and {y.shape[0]} (row i of x belongs to row i of y)")
     n = int(x.shape[0])
@@ -1169,7 +1095,6 @@ def pair_dependence(x, y, kernel, bw2x=None, bw2y=None, perm=None):
     if x.device != y.device or (perm is not None and perm.device != x.device):
         raise ValueError("x, y and perm must be on one device")
     (bwx_arg, bwx_host), (bwy_arg, bwy_host) = _side_bandwidth(kernel, bw2x, "bw2x"), _side_bandwidth(kernel, bw2y, "bw2y")
-    lib = _lib.load()
     x, y = as_matrix(x, "x"), as_matrix(y, "y")
     dev = _same_device(x, y)
     if perm is not None:
@@ -1177,11 +1102,9 @@ def pair_dependence(x, y, kernel, bw2x=None, bw2y=None, perm=None):
         perm = perm.contiguous()
     rows = torch.empty((n, 5), dtype=torch.float64, device=dev)
     sums = torch.empty(8, dtype=torch.float64, device=dev)
-    nb = lib.am_pair_dependence_workspace_bytes(n, x.shape[1], y.shape[1])
-    ws = _workspace(nb, dev)
-    _call(lib, "am_pair_dependence_f32", dev, _ptr(x), n, _ld(x), x.shape[1], _ptr(y), _ld(y), y.shape[1],
-          _ptr(perm) if perm is not None else ctypes.c_void_p(None), MMD_KERNELS[kernel], bwx_arg, bwx_host, bwy_arg, bwy_host,
-          _ptr(rows), _ptr(sums), _ptr(ws), nb)
+    _run("am_pair_dependence_f32", dev, "am_pair_dependence_workspace_bytes", (n, x.shape[1], y.shape[1]), _ptr(x), n, _ld(x),
+         x.shape[1], _ptr(y), _ld(y), y.shape[1], _opt(perm), MMD_KERNELS[kernel], bwx_arg, bwx_host, bwy_arg, bwy_host, _ptr(rows),
+         _ptr(sums))
     return rows, sums
 
 
@@ -1195,10 +1118,9 @@ def mmd_rbf_group_sums(x, idx, offsets, y, bw2=None, gamma=None, rows=False):
     group, Sxy_b over all n_b N2 pairs), out_rows the f64 device tensor [n_total, 2] of the row sums {w_i, c_i} in LIST
     order, and check() the one host read of the workspace's flag word, which raises ValueError for an index outside
     [0, N1) (the kernels never dereference it)."""
-    lib = _lib.load()
-    kind = _kad_kind("mmd_rbf_group_sums", x, y)
+    f64 = _both_f64("mmd_rbf_group_sums", x, y)
     bw2_arg, gamma_arg = _bandwidth_args(bw2, gamma)
-    (x, ldx), (y, ldy) = _kad_matrix(kind, x, "x"), _kad_matrix(kind, y, "y")
+    (x, ldx, kind), (y, ldy, _) = _rows(x, "x", f64), _rows(y, "y", f64)
     dev = _same_device(x, y)
     n, d = x.shape
     if d != y.shape[1]:
@@ -1207,13 +1129,8 @@ def mmd_rbf_group_sums(x, idx, offsets, y, bw2=None, gamma=None, rows=False):
     idx = _group_index(idx, offs[-1], x)
     out_groups = torch.empty((b, 2), dtype=torch.float64, device=dev)
     out_rows = torch.empty((offs[-1], 2), dtype=torch.float64, device=dev) if rows else None
-    query = lib.am_mmd_rbf_groups_f64_workspace_bytes if kind == "f64" else lib.am_mmd_rbf_groups_workspace_bytes
-    nb = query(offs[-1], b, y.shape[0], d)
-    ws = _workspace(nb, dev)
-    null = ctypes.c_void_p(None)
-    _call(lib, "am_mmd_rbf_groups_" + kind, dev, _ptr(x), n, ldx, _ptr(idx) if idx is not None else null,
-          ctypes.cast(host_offs, ctypes.c_void_p), b, _ptr(y), y.shape[0], ldy, d, bw2_arg, gamma_arg, _ptr(out_groups),
-          _ptr(out_rows) if rows else null, _ptr(ws), nb)
+    ws = _run("am_mmd_rbf_groups_" + kind, dev, _query("mmd_rbf_groups", f64), (offs[-1], b, y.shape[0], d), _ptr(x), n, ldx,
+              _opt(idx), _host(host_offs), b, _ptr(y), y.shape[0], ldy, d, bw2_arg, gamma_arg, _ptr(out_groups), _opt(out_rows))
     check = _index_check(ws, idx, n, "group rows")
     return (out_groups, out_rows, check) if rows else (out_groups, check)
 
@@ -1258,32 +1175,19 @@ def knn_radii(x, k, columns=None, prepared=None):
     """(k+1)-th smallest distance from each row of x to the rows of `columns`
     (default: x itself) - prdc.py:4-14, in the dtype of the rows (float64 rows: float64 radii, am_knn_radii_f64).
     `prepared`: the PreparedSet of x (self-distance form of float32 sets only)."""
-    lib = _lib.load()
-    if is_f64(x) or is_f64(columns):
-        x = as_matrix64(x)
-        y = x if columns is None else as_matrix64(columns, "columns")
-        n, d = x.shape
-        if y.shape[1] != d:
-            raise ValueError("feature dimensions differ")
-        out = torch.empty(n, dtype=torch.float64, device=x.device)
-        nb = lib.am_knn_f64_workspace_bytes(n, y.shape[0], d, int(k))
-        ws = _workspace(nb, x.device)
-        _call(lib, "am_knn_radii_f64", x.device, _ptr(x), n, _ld64(x), _ptr(y), y.shape[0], _ld64(y), d, int(k), _ptr(out), _ptr(ws), nb)
-        return out
-    x = as_matrix(x)
-    y = x if columns is None else as_matrix(columns, "columns")
+    f64 = _any_f64(x, columns)
+    x, ldx, kind = _rows(x, "embeddings", f64)
+    y, ldy = (x, ldx) if columns is None else _rows(columns, "columns", f64)[:2]
     n, d = x.shape
     if y.shape[1] != d:
         raise ValueError("feature dimensions differ")
-    out = torch.empty(n, dtype=torch.float32, device=x.device)
-    nb = lib.am_knn_workspace_bytes(n, y.shape[0], d, int(k))
-    ws = _workspace(nb, x.device)
-    if prepared is not None and columns is None:
+    out = torch.empty(n, dtype=x.dtype, device=x.device)
+    query = _query("knn", f64), (n, y.shape[0], d, int(k))
+    if prepared is not None and columns is None and not f64:
         ps = prepared.struct()
-        _call(lib, "am_knn_radii_prepared_f32", x.device, _ptr(x), n, _ld(x), d, ctypes.byref(ps), int(k), _ptr(out), _ptr(ws), nb)
-        return out
-    _call(lib, "am_knn_radii_f32", x.device, _ptr(x), n, _ld(x), _ptr(y), y.shape[0], _ld(y), d, int(k), _ptr(out),
-                                    _ptr(ws), nb)
+        _run("am_knn_radii_prepared_f32", x.device, *query, _ptr(x), n, ldx, d, ctypes.byref(ps), int(k), _ptr(out))
+    else:
+        _run("am_knn_radii_" + kind, x.device, *query, _ptr(x), n, ldx, _ptr(y), y.shape[0], ldy, d, int(k), _ptr(out))
     return out
 
 
@@ -1304,40 +1208,26 @@ def _check_row_labels(x, y, x_group, y_group):
 def _knn_search(op, x, y, k, squared, self_offset=None, groups=None):
     """knn_search (groups is None: exclusion by index) and knn_search_groups (groups = (x_group, y_group)); `op` names the
     caller in the messages."""
-    if is_f64(x) or is_f64(y):
-        raise NotImplementedError(f"{op} takes float32 rows (the float64 matrix-core form is not implemented)")
+    _refuse_f64(op, x, y)
     k = int(k)
     if not 1 <= k <= KNN_SEARCH_MAX_K:
         raise ValueError(f"k={k} must be in 1 .. {KNN_SEARCH_MAX_K}")
-    if x.dim() != 2 or y.dim() != 2:
-        raise ValueError(f"x and y must be 2-D, got shapes {tuple(x.shape)} and {tuple(y.shape)}")
-    if x.shape[1] != y.shape[1]:
-        raise ValueError(f"feature widths differ: {x.shape[1]} and {y.shape[1]}")
+    _check_two_sets(op, x, y, sides=False)
     if x.shape[0] < 1 or y.shape[0] < 1:
         raise ValueError(f"{op} needs rows on both sides (got {x.shape[0]} and {y.shape[0]})")
     if groups is not None:
         _check_row_labels(x, y, *groups)
-    lib = _lib.load()
-    same = x is y
-    x = as_matrix(x, "x")
-    y = x if same else as_matrix(y, "y")
-    dev = _same_device(x, y)
-    n, d = x.shape
-    m = y.shape[0]
+    x, y, dev, n, m, d = _two_sets(x, y)
     dist = torch.empty((n, k), dtype=torch.float32, device=dev)
     idx = torch.empty((n, k), dtype=torch.int64, device=dev)
     out = (1 if squared else 0, _ptr(dist), _ptr(idx))
     if groups is None:
-        nb = lib.am_knn_search_workspace_bytes(n, m, d, k)
-        ws = _workspace(nb, dev)
-        _call(lib, "am_knn_search_f32", dev, _ptr(x), n, _ld(x), _ptr(y), m, _ld(y), d, k,
-              -1 if self_offset is None else int(self_offset), *out, _ptr(ws), nb)
+        _run("am_knn_search_f32", dev, "am_knn_search_workspace_bytes", (n, m, d, k), _ptr(x), n, _ld(x), _ptr(y), m, _ld(y), d, k,
+             -1 if self_offset is None else int(self_offset), *out)
     else:
         x_group, y_group = (g.contiguous() for g in groups)
-        nb = lib.am_knn_search_groups_workspace_bytes(n, m, d, k)
-        ws = _workspace(nb, dev)
-        _call(lib, "am_knn_search_groups_f32", dev, _ptr(x), n, _ld(x), _ptr(x_group), _ptr(y), m, _ld(y), _ptr(y_group), d, k,
-              *out, _ptr(ws), nb)
+        _run("am_knn_search_groups_f32", dev, "am_knn_search_groups_workspace_bytes", (n, m, d, k), _ptr(x), n, _ld(x), _ptr(x_group),
+             _ptr(y), m, _ld(y), _ptr(y_group), d, k, *out)
     return dist, idx
 
 
@@ -1369,29 +1259,16 @@ def knn_search_chunks(n, m, d, k):
 def _sample_scores(op, x, y, r_y, groups=None):
     """sample_scores (groups is None: every pair counts) and sample_scores_groups (groups = (x_group, y_group)); `op` names
     the caller in the messages."""
-    if is_f64(x) or is_f64(y) or is_f64(r_y):
-        raise NotImplementedError(f"{op} takes float32 rows (the float64 matrix-core form is not implemented)")
-    if x.dim() != 2 or y.dim() != 2:
-        raise ValueError(f"x and y must be 2-D, got shapes {tuple(x.shape)} and {tuple(y.shape)}")
-    if x.shape[1] != y.shape[1]:
-        raise ValueError(f"feature widths differ: {x.shape[1]} and {y.shape[1]}")
-    if x.shape[0] < 1 or y.shape[0] < 1 or x.shape[1] < 1:
-        raise ValueError(f"{op} needs rows on both sides (got shapes {tuple(x.shape)} and {tuple(y.shape)})")
+    _refuse_f64(op, x, y, r_y)
+    _check_two_sets(op, x, y)
     if not torch.is_tensor(r_y) or r_y.dim() != 1 or r_y.shape[0] != y.shape[0] or r_y.dtype != torch.float32:
         raise ValueError(f"r_y must be a float32 tensor with one radius per row of y ({y.shape[0]}), got "
                          f"{tuple(r_y.shape) if torch.is_tensor(r_y) else type(r_y).__name__}"
                          f"{' ' + str(r_y.dtype) if torch.is_tensor(r_y) else ''}")
     if groups is not None:
         _check_row_labels(x, y, *groups)
-    lib = _lib.load()
-    same = x is y
-    x = as_matrix(x, "x")
-    y = x if same else as_matrix(y, "y")
-    _require_cuda(r_y, "r_y")
-    dev = _same_device(x, y, r_y)
+    x, y, dev, n, m, d = _two_sets(x, y, more=((r_y, "r_y"),))
     r_y = r_y.contiguous()
-    n, d = x.shape
-    m = y.shape[0]
     realism = torch.empty(n, dtype=torch.float32, device=dev)
     realism_idx = torch.empty(n, dtype=torch.int64, device=dev)
     count = torch.empty(n, dtype=torch.int32, device=dev)
@@ -1399,15 +1276,11 @@ def _sample_scores(op, x, y, r_y, groups=None):
     rarity_idx = torch.empty(n, dtype=torch.int64, device=dev)
     out = (_ptr(r_y), _ptr(realism), _ptr(realism_idx), _ptr(count), _ptr(rarity), _ptr(rarity_idx))
     if groups is None:
-        nb = lib.am_sample_scores_workspace_bytes(n, m, d)
-        ws = _workspace(nb, dev)
-        _call(lib, "am_sample_scores_f32", dev, _ptr(x), n, _ld(x), _ptr(y), m, _ld(y), d, *out, _ptr(ws), nb)
+        _run("am_sample_scores_f32", dev, "am_sample_scores_workspace_bytes", (n, m, d), _ptr(x), n, _ld(x), _ptr(y), m, _ld(y), d, *out)
     else:
         x_group, y_group = (g.contiguous() for g in groups)
-        nb = lib.am_sample_scores_groups_workspace_bytes(n, m, d)
-        ws = _workspace(nb, dev)
-        _call(lib, "am_sample_scores_groups_f32", dev, _ptr(x), n, _ld(x), _ptr(x_group), _ptr(y), m, _ld(y), _ptr(y_group), d,
-              *out, _ptr(ws), nb)
+        _run("am_sample_scores_groups_f32", dev, "am_sample_scores_groups_workspace_bytes", (n, m, d), _ptr(x), n, _ld(x), _ptr(x_group),
+             _ptr(y), m, _ld(y), _ptr(y_group), d, *out)
     return realism, realism_idx, count, rarity, rarity_idx
 
 
@@ -1448,31 +1321,17 @@ def psr_scores(x, y, radius, sums=True):
     range, 1.0 on a row of y); sums = { sum psr, sum count } in a fixed tree (sums=False: not computed).  The squared
     distances have the bits of knn_search(x, y, ., squared=True); `x is y` computes the norms once.  Two calls at the same
     shapes return the same bits; the last bits of psr depend on the chunk plan (psr_chunks)."""
-    if is_f64(x) or is_f64(y):
-        raise NotImplementedError("psr_scores takes float32 rows (the float64 matrix-core form is not implemented)")
-    if x.dim() != 2 or y.dim() != 2:
-        raise ValueError(f"x and y must be 2-D, got shapes {tuple(x.shape)} and {tuple(y.shape)}")
-    if x.shape[1] != y.shape[1]:
-        raise ValueError(f"feature widths differ: {x.shape[1]} and {y.shape[1]}")
-    if x.shape[0] < 1 or y.shape[0] < 1 or x.shape[1] < 1:
-        raise ValueError(f"psr_scores needs rows on both sides (got shapes {tuple(x.shape)} and {tuple(y.shape)})")
+    _refuse_f64("psr_scores", x, y)
+    _check_two_sets("psr_scores", x, y)
     radius = float(radius)
     if not (math.isfinite(radius) and radius > 0.0 and radius * radius <= PSR_RADIUS_SQ_MAX):
         raise ValueError(f"radius={radius} must be finite and > 0, with radius^2 a finite float32 number")
-    lib = _lib.load()
-    same = x is y
-    x = as_matrix(x, "x")
-    y = x if same else as_matrix(y, "y")
-    dev = _same_device(x, y)
-    n, d = x.shape
-    m = y.shape[0]
+    x, y, dev, n, m, d = _two_sets(x, y)
     psr = torch.empty(n, dtype=torch.float64, device=dev)
     count = torch.empty(n, dtype=torch.int32, device=dev)
     totals = torch.empty(2, dtype=torch.float64, device=dev) if sums else None
-    nb = lib.am_psr_workspace_bytes(n, m, d)
-    ws = _workspace(nb, dev)
-    _call(lib, "am_psr_f32", dev, _ptr(x), n, _ld(x), _ptr(y), m, _ld(y), d, radius, _ptr(psr), _ptr(count),
-          _ptr(totals) if sums else None, _ptr(ws), nb)
+    _run("am_psr_f32", dev, "am_psr_workspace_bytes", (n, m, d), _ptr(x), n, _ld(x), _ptr(y), m, _ld(y), d, radius, _ptr(psr),
+         _ptr(count), _opt(totals))
     return psr, count, totals
 
 
@@ -1506,25 +1365,13 @@ def retrieval_ranks(q, g, pos_start, pos_count, pos_columns, cosine=True, groups
     positive, or with a positive outside [0, M), is unranked: (-1, -1, NaN, -1).  groups = (q_group, g_group), int32 device
     vectors: a column of the row's own group is no negative (a positive there is still a positive).  `q is g` computes the
     norms once.  Two calls return the same bits."""
-    if is_f64(q) or is_f64(g):
-        raise NotImplementedError("retrieval_ranks takes float32 rows (the float64 matrix-core form is not implemented)")
-    if q.dim() != 2 or g.dim() != 2:
-        raise ValueError(f"q and g must be 2-D, got shapes {tuple(q.shape)} and {tuple(g.shape)}")
-    if q.shape[1] != g.shape[1]:
-        raise ValueError(f"feature widths differ: {q.shape[1]} and {g.shape[1]}")
-    if q.shape[0] < 1 or g.shape[0] < 1 or q.shape[1] < 1:
-        raise ValueError(f"retrieval_ranks needs rows on both sides (got shapes {tuple(q.shape)} and {tuple(g.shape)})")
+    _refuse_f64("retrieval_ranks", q, g)
+    _check_two_sets("retrieval_ranks", q, g, both="q and g")
     if groups is not None:
         _check_row_labels(q, g, *groups)
-    lib = _lib.load()
-    same = q is g
-    q = as_matrix(q, "q")
-    g = q if same else as_matrix(g, "g")
-    dev = _same_device(q, g)
+    q, g, dev, n, m, d = _two_sets(q, g, ("q", "g"))
     _check_segments(q, pos_start, pos_count, pos_columns)
     pos_start, pos_count, pos_columns = pos_start.contiguous(), pos_count.contiguous(), pos_columns.contiguous()
-    n, d = q.shape
-    m = g.shape[0]
     better = torch.empty(n, dtype=torch.int32, device=dev)
     tied = torch.empty(n, dtype=torch.int32, device=dev)
     score = torch.empty(n, dtype=torch.float32, device=dev)
@@ -1532,12 +1379,10 @@ def retrieval_ranks(q, g, pos_start, pos_count, pos_columns, cosine=True, groups
     n_pos = torch.empty(n, dtype=torch.int32, device=dev)
     n_pos_own = torch.empty(n, dtype=torch.int32, device=dev)
     q_group, g_group = (t.contiguous() for t in groups) if groups is not None else (None, None)
-    nb = lib.am_retrieval_workspace_bytes(n, m, d)
-    ws = _workspace(nb, dev)
-    _call(lib, "am_retrieval_ranks_f32", dev, _ptr(q), n, _ld(q), _ptr(g), m, _ld(g), d, 1 if cosine else 0,
-          _ptr(pos_start), _ptr(pos_count), _ptr(pos_columns) if pos_columns.numel() else None, int(pos_columns.numel()),
-          _ptr(q_group) if groups is not None else None, _ptr(g_group) if groups is not None else None,
-          _ptr(better), _ptr(tied), _ptr(score), _ptr(positive), _ptr(n_pos), _ptr(n_pos_own), _ptr(ws), nb)
+    _run("am_retrieval_ranks_f32", dev, "am_retrieval_workspace_bytes", (n, m, d), _ptr(q), n, _ld(q), _ptr(g), m, _ld(g), d,
+         1 if cosine else 0, _ptr(pos_start), _ptr(pos_count), _opt(pos_columns if pos_columns.numel() else None),
+         int(pos_columns.numel()), _opt(q_group), _opt(g_group), _ptr(better), _ptr(tied), _ptr(score), _ptr(positive), _ptr(n_pos),
+         _ptr(n_pos_own))
     return better, tied, score, positive, n_pos, n_pos_own
 
 
@@ -1548,12 +1393,8 @@ def retrieval_chunks(n, m, d):
 
 # ---- k-means: the two halves of a Lloyd iteration (csrc/kmeans.hip) ----
 def _kmeans_check(what, x, c):
-    if is_f64(x) or is_f64(c):
-        raise NotImplementedError(f"{what} takes float32 rows (the float64 matrix-core form is not implemented)")
-    if x.dim() != 2 or c.dim() != 2:
-        raise ValueError(f"rows and centroids must be 2-D, got shapes {tuple(x.shape)} and {tuple(c.shape)}")
-    if x.shape[1] != c.shape[1]:
-        raise ValueError(f"feature widths differ: {x.shape[1]} and {c.shape[1]}")
+    _refuse_f64(what, x, c)
+    _check_two_sets(what, x, c, both="rows and centroids", sides=False)
     if c.shape[0] < 1:
         raise ValueError(f"{what} needs at least one centroid (K={c.shape[0]})")
     if x.shape[0] < 1 or x.shape[1] < 1:
@@ -1566,18 +1407,12 @@ def kmeans_assign(x, c):
     knn_search(x, c, 1, squared=True); ties go to the smallest centroid index; a row without a finite distance is
     (-1, +inf) and is left out of inertia, the f64 sum of d2 added in a fixed order."""
     _kmeans_check("kmeans_assign", x, c)
-    lib = _lib.load()
-    x, c = as_matrix(x, "x"), as_matrix(c, "c")
-    dev = _same_device(x, c)
-    n, d = x.shape
-    k = c.shape[0]
+    x, c, dev, n, k, d = _two_sets(x, c, ("x", "c"))
     labels = torch.empty(n, dtype=torch.int64, device=dev)
     d2 = torch.empty(n, dtype=torch.float32, device=dev)
     inertia = torch.empty((), dtype=torch.float64, device=dev)
-    nb = lib.am_kmeans_assign_workspace_bytes(n, k, d)
-    ws = _workspace(nb, dev)
-    _call(lib, "am_kmeans_assign_f32", dev, _ptr(x), n, _ld(x), _ptr(c), k, _ld(c), d, _ptr(labels), _ptr(d2), _ptr(inertia),
-          _ptr(ws), nb)
+    _run("am_kmeans_assign_f32", dev, "am_kmeans_assign_workspace_bytes", (n, k, d), _ptr(x), n, _ld(x), _ptr(c), k, _ld(c), d,
+         _ptr(labels), _ptr(d2), _ptr(inertia))
     return labels, d2, inertia
 
 
@@ -1590,22 +1425,15 @@ def kmeans_update(x, labels, c_old):
     if not torch.is_tensor(labels) or labels.dim() != 1 or labels.shape[0] != x.shape[0] or labels.dtype != torch.int64:
         raise ValueError(f"labels must be an int64 tensor with one entry per row ({x.shape[0]}), got "
                          f"{getattr(labels, 'dtype', type(labels).__name__)} {tuple(getattr(labels, 'shape', ()))}")
-    lib = _lib.load()
-    x, c_old = as_matrix(x, "x"), as_matrix(c_old, "c_old")
-    _require_cuda(labels, "labels")
-    dev = _same_device(x, c_old, labels)
-    n, d = x.shape
-    k = c_old.shape[0]
+    x, c_old, dev, n, k, d = _two_sets(x, c_old, ("x", "c_old"), more=((labels, "labels"),))
     labels = labels.contiguous()
     ordered, order = torch.sort(labels, stable=True)                       # rows with label -1 come first
     offsets = torch.searchsorted(ordered, torch.arange(k + 1, dtype=torch.int64, device=dev))
     ld = (d + 3) // 4 * 4
     c_new = torch.empty((k, ld), dtype=torch.float32, device=dev)[:, :d]
     counts = torch.empty(k, dtype=torch.int64, device=dev)
-    nb = lib.am_kmeans_update_workspace_bytes(n, k, d)
-    ws = _workspace(nb, dev)
-    _call(lib, "am_kmeans_update_f32", dev, _ptr(x), n, _ld(x), d, _ptr(labels), _ptr(order), _ptr(offsets), k, _ptr(c_old),
-          _ld(c_old), _ptr(c_new), ld, _ptr(counts), _ptr(ws), nb)
+    _run("am_kmeans_update_f32", dev, "am_kmeans_update_workspace_bytes", (n, k, d), _ptr(x), n, _ld(x), d, _ptr(labels), _ptr(order),
+         _ptr(offsets), k, _ptr(c_old), _ld(c_old), _ptr(c_new), ld, _ptr(counts))
     return c_new, counts
 
 
@@ -1621,14 +1449,8 @@ def softmin(x, y, g=None, eps=None, prev=None, damping=0.0):
     (damping == 0: T itself); change = max |out - prev| (prev None: max |out|), magnitude = max |out|.  The squared
     distances have the bits of knn_search(x, y, ., squared=True); `x is y` computes the norms once.  Two calls return the
     same bits."""
-    if is_f64(x) or is_f64(y):
-        raise NotImplementedError("softmin takes float32 rows (the float64 matrix-core form is not implemented)")
-    if x.dim() != 2 or y.dim() != 2:
-        raise ValueError(f"x and y must be 2-D, got shapes {tuple(x.shape)} and {tuple(y.shape)}")
-    if x.shape[1] != y.shape[1]:
-        raise ValueError(f"feature widths differ: {x.shape[1]} and {y.shape[1]}")
-    if x.shape[0] < 1 or y.shape[0] < 1 or x.shape[1] < 1:
-        raise ValueError(f"softmin needs rows on both sides (got shapes {tuple(x.shape)} and {tuple(y.shape)})")
+    _refuse_f64("softmin", x, y)
+    _check_two_sets("softmin", x, y)
     if eps is None or not math.isfinite(float(eps)) or float(eps) <= 0.0:
         raise ValueError(f"eps={eps!r} must be a finite positive number")
     eps, damping = float(eps), float(damping)
@@ -1640,27 +1462,13 @@ def softmin(x, y, g=None, eps=None, prev=None, damping=0.0):
         raise ValueError(f"prev must be a float64 tensor with one value per row of x ({x.shape[0]})")
     if damping != 0.0 and prev is None:
         raise ValueError(f"damping={damping!r} needs prev")
-    lib = _lib.load()
-    same = x is y
-    x = as_matrix(x, "x")
-    y = x if same else as_matrix(y, "y")
-    vectors = []
-    for t, name in ((g, "g"), (prev, "prev")):
-        if t is not None:
-            _require_cuda(t, name)
-            t = t.contiguous()
-            vectors.append(t)
-    dev = _same_device(x, y, *vectors)
+    x, y, dev, n, m, d = _two_sets(x, y, more=[(t, name) for t, name in ((g, "g"), (prev, "prev")) if t is not None])
     g = g.contiguous() if g is not None else None
     prev = prev.contiguous() if prev is not None else None
-    n, d = x.shape
-    m = y.shape[0]
     out = torch.empty(n, dtype=torch.float64, device=dev)
     stats = torch.empty(2, dtype=torch.float64, device=dev)
-    nb = lib.am_softmin_workspace_bytes(n, m, d)
-    ws = _workspace(nb, dev)
-    _call(lib, "am_softmin_f32", dev, _ptr(x), n, _ld(x), _ptr(y), m, _ld(y), d, _ptr(g) if g is not None else None, eps,
-          _ptr(prev) if prev is not None else None, damping, _ptr(out), _ptr(stats), _ptr(ws), nb)
+    _run("am_softmin_f32", dev, "am_softmin_workspace_bytes", (n, m, d), _ptr(x), n, _ld(x), _ptr(y), m, _ld(y), d, _opt(g), eps,
+         _opt(prev), damping, _ptr(out), _ptr(stats))
     return out, stats[0], stats[1]
 
 
@@ -1673,17 +1481,6 @@ def _fld_vector_ok(t, rows):
     return torch.is_tensor(t) and t.dim() == 1 and t.shape[0] == rows and t.dtype == torch.float64
 
 
-def _fld_matrices(x, g, name):
-    if is_f64(x) or is_f64(g):
-        raise NotImplementedError(f"{name} takes float32 rows (the float64 matrix-core form is not implemented)")
-    if x.dim() != 2 or g.dim() != 2:
-        raise ValueError(f"x and g must be 2-D, got shapes {tuple(x.shape)} and {tuple(g.shape)}")
-    if x.shape[1] != g.shape[1]:
-        raise ValueError(f"feature widths differ: {x.shape[1]} and {g.shape[1]}")
-    if x.shape[0] < 1 or g.shape[0] < 1 or x.shape[1] < 1:
-        raise ValueError(f"{name} needs rows on both sides (got shapes {tuple(x.shape)} and {tuple(g.shape)})")
-
-
 def fld_loglik(x, g, theta, stats=None):
     """l_i = logsumexp_j (-h_j d2(x_i, g_j) - c_j) - log M - (D / 2) log 2 pi for every row of x under the mixture of
     isotropic Gaussians on the M rows of g with log-variances theta (float64 [M]; h = 0.5 exp(-theta), c = (D / 2) theta)
@@ -1692,26 +1489,19 @@ def fld_loglik(x, g, theta, stats=None):
     write the three numbers into (a row of a fit's history).  The squared distances have the bits of
     knn_search(x, g, ., squared=True); a row with a non-finite element has l = -inf, a centre with one contributes 0.  Two
     calls return the same bits."""
-    _fld_matrices(x, g, "fld_loglik")
+    _refuse_f64("fld_loglik", x, g)
+    _check_two_sets("fld_loglik", x, g, both="x and g")
     if not _fld_vector_ok(theta, g.shape[0]):
         raise ValueError(f"theta must be a float64 tensor with one log-variance per row of g ({g.shape[0]})")
     if stats is not None and not (_fld_vector_ok(stats, 3) and stats.is_contiguous()):
         raise ValueError("stats must be a contiguous float64 tensor of 3 elements")
-    lib = _lib.load()
-    x, g = as_matrix(x, "x"), as_matrix(g, "g")
-    _require_cuda(theta, "theta")
+    x, g, dev, n, m, d = _two_sets(x, g, ("x", "g"), more=[(theta, "theta")] + ([] if stats is None else [(stats, "stats")]))
     theta = theta.contiguous()
-    if stats is not None:
-        _require_cuda(stats, "stats")
-    dev = _same_device(x, g, theta, *(() if stats is None else (stats,)))
-    n, d = x.shape
-    m = g.shape[0]
     out = torch.empty(n, dtype=torch.float64, device=dev)
     if stats is None:
         stats = torch.empty(3, dtype=torch.float64, device=dev)
-    nb = lib.am_fld_loglik_workspace_bytes(n, m, d)
-    ws = _workspace(nb, dev)
-    _call(lib, "am_fld_loglik_f32", dev, _ptr(x), n, _ld(x), _ptr(g), m, _ld(g), d, _ptr(theta), _ptr(out), _ptr(stats), _ptr(ws), nb)
+    _run("am_fld_loglik_f32", dev, "am_fld_loglik_workspace_bytes", (n, m, d), _ptr(x), n, _ld(x), _ptr(g), m, _ld(g), d, _ptr(theta),
+         _ptr(out), _ptr(stats))
     return out, stats
 
 
@@ -1722,7 +1512,8 @@ def fld_grad_step(g, x, theta, lse, n_finite, m, v, step, lr, theta_min):
     tensor of one element, its stats[1].  A_j = sum_i r_ij and B_j = sum_i r_ij d2_ij over the responsibilities r_ij; the
     gradient is -(h_j B_j - (D / 2) A_j) / n_finite and the update that of metrics.fld.fld_adam_step with step >= 1, clamped
     to [theta_min, 30].  Two calls return the same bits."""
-    _fld_matrices(x, g, "fld_grad_step")
+    _refuse_f64("fld_grad_step", x, g)
+    _check_two_sets("fld_grad_step", x, g, both="x and g")
     for t, name, rows in ((theta, "theta", g.shape[0]), (m, "m", g.shape[0]), (v, "v", g.shape[0]), (lse, "lse", x.shape[0])):
         if not _fld_vector_ok(t, rows):
             raise ValueError(f"{name} must be a float64 tensor of {rows} elements")
@@ -1736,22 +1527,13 @@ def fld_grad_step(g, x, theta, lse, n_finite, m, v, step, lr, theta_min):
     if not math.isfinite(theta_min) or not FLD_THETA_MIN_LIMIT <= theta_min <= FLD_THETA_MAX:
         raise ValueError(f"theta_min={theta_min!r} must lie in [{FLD_THETA_MIN_LIMIT:.4f}, {FLD_THETA_MAX}]: "
                          "0.5 exp(-theta) has to stay a normal float32 number")
-    lib = _lib.load()
-    g, x = as_matrix(g, "g"), as_matrix(x, "x")
-    vectors = []
-    for t, name in ((theta, "theta"), (lse, "lse"), (n_finite, "n_finite"), (m, "m"), (v, "v")):
-        _require_cuda(t, name)
-        vectors.append(t.contiguous())
-    theta, lse, n_finite = vectors[:3]
-    dev = _same_device(g, x, *vectors)
-    m, v = vectors[3].clone(), vectors[4].clone()                    # the kernel updates its moments in place
-    rows, d = g.shape
-    n = x.shape[0]
+    vectors = ((theta, "theta"), (lse, "lse"), (n_finite, "n_finite"), (m, "m"), (v, "v"))
+    g, x, dev, rows, n, d = _two_sets(g, x, ("g", "x"), more=vectors)
+    theta, lse, n_finite, m, v = (t.contiguous() for t, _ in vectors)
+    m, v = m.clone(), v.clone()                                      # the kernel updates its moments in place
     theta_out, a, b = (torch.empty(rows, dtype=torch.float64, device=dev) for _ in range(3))
-    nb = lib.am_fld_grad_workspace_bytes(rows, n, d)
-    ws = _workspace(nb, dev)
-    _call(lib, "am_fld_grad_f32", dev, _ptr(g), rows, _ld(g), _ptr(x), n, _ld(x), d, _ptr(theta), _ptr(lse), _ptr(n_finite), _ptr(m),
-          _ptr(v), step, lr, theta_min, _ptr(theta_out), _ptr(a), _ptr(b), _ptr(ws), nb)
+    _run("am_fld_grad_f32", dev, "am_fld_grad_workspace_bytes", (rows, n, d), _ptr(g), rows, _ld(g), _ptr(x), n, _ld(x), d, _ptr(theta),
+         _ptr(lse), _ptr(n_finite), _ptr(m), _ptr(v), step, lr, theta_min, _ptr(theta_out), _ptr(a), _ptr(b))
     return theta_out, m, v, a, b
 
 
@@ -1760,12 +1542,8 @@ def sliced_project(x, theta):
     """z[l, i] = <theta_l, x_i> for the rows of x [N, D] and the directions theta [L, D] (am_sliced_project_f32): float32
     [L, N] as a device tensor, stream-ordered, nothing waits for the device.  A projection's bits do not depend on which
     other directions share the call."""
-    if is_f64(x) or is_f64(theta):
-        raise NotImplementedError("sliced_project takes float32 rows (the float64 matrix-core form is not implemented)")
-    if x.dim() != 2 or theta.dim() != 2:
-        raise ValueError(f"rows and directions must be 2-D, got shapes {tuple(x.shape)} and {tuple(theta.shape)}")
-    if x.shape[1] != theta.shape[1]:
-        raise ValueError(f"feature widths differ: {x.shape[1]} and {theta.shape[1]}")
+    _refuse_f64("sliced_project", x, theta)
+    _check_two_sets("sliced_project", x, theta, both="rows and directions", sides=False)
     if x.shape[0] < 1 or theta.shape[0] < 1 or x.shape[1] < 1:
         raise ValueError(f"sliced_project needs rows and directions (got shapes {tuple(x.shape)} and {tuple(theta.shape)})")
     lib = _lib.load()
@@ -1779,8 +1557,7 @@ def sliced_project(x, theta):
 
 
 def _sorted_matrix(z, name):
-    if is_f64(z):
-        raise NotImplementedError(f"{name} takes float32 rows (the float64 matrix-core form is not implemented)")
+    _refuse_f64(name, z)
     if not torch.is_tensor(z) or z.dim() != 2 or z.shape[0] < 1 or z.shape[1] < 1:
         raise ValueError(f"{name} needs a 2-D tensor with rows and columns (got {tuple(getattr(z, 'shape', ()))})")
 
@@ -1802,7 +1579,6 @@ def sort_rows(z, out=None):
     nothing waits for the device.  -0.0 before +0.0, NaNs last as the canonical quiet NaN.  out=z sorts in place (z must then
     be float32 with unit column stride); the workspace is one more [L, N] matrix."""
     _sorted_matrix(z, "sort_rows")
-    lib = _lib.load()
     src = _unit_columns(z, "z")
     if out is None:
         out = torch.empty(tuple(src.shape), dtype=torch.float32, device=src.device)
@@ -1811,11 +1587,9 @@ def sort_rows(z, out=None):
             raise ValueError("sort_rows: an in-place sort needs a float32 tensor with unit column stride")
     else:
         raise ValueError("sort_rows: out must be None or z itself")
-    dev = src.device
     nl, n = src.shape
-    nb = lib.am_sort_rows_workspace_bytes(nl, n)
-    ws = _workspace(nb, dev)
-    _call(lib, "am_sort_rows_f32", dev, _ptr(src), nl, n, _row_stride(src), _ptr(out), _row_stride(out), _ptr(ws), nb)
+    _run("am_sort_rows_f32", src.device, "am_sort_rows_workspace_bytes", (nl, n), _ptr(src), nl, n, _row_stride(src), _ptr(out),
+         _row_stride(out))
     return out
 
 
@@ -1833,7 +1607,6 @@ def sliced_w(zx_sorted, zy_sorted, p=2):
     n, m = int(zx_sorted.shape[1]), int(zy_sorted.shape[1])
     if n * m >= 1 << 53:
         raise ValueError(f"n * m = {n} * {m} must stay below 2^53 (the coupling's weights are exact integers)")
-    lib = _lib.load()
     same = zx_sorted is zy_sorted
     zx = _unit_columns(zx_sorted, "zx_sorted")
     zy = zx if same else _unit_columns(zy_sorted, "zy_sorted")
@@ -1841,21 +1614,14 @@ def sliced_w(zx_sorted, zy_sorted, p=2):
     nl = zx.shape[0]
     w = torch.empty(nl, dtype=torch.float64, device=dev)
     bad = torch.empty(nl, dtype=torch.int32, device=dev)
-    nb = lib.am_sliced_w_workspace_bytes(nl, n, m)
-    ws = _workspace(nb, dev)
-    _call(lib, "am_sliced_w_f32", dev, _ptr(zx), n, _row_stride(zx), _ptr(zy), m, _row_stride(zy), nl, int(p), _ptr(w), _ptr(bad),
-          _ptr(ws), nb)
+    _run("am_sliced_w_f32", dev, "am_sliced_w_workspace_bytes", (nl, n, m), _ptr(zx), n, _row_stride(zx), _ptr(zy), m, _row_stride(zy),
+         nl, int(p), _ptr(w), _ptr(bad))
     return w, bad
 
 
 # ---- random Fourier features of the Gaussian kernel and their moment matrix (csrc/rff.hip) ----
-_RFF_CAPS = {}
-
-
 def rff_max_features():
-    if "features" not in _RFF_CAPS:
-        _RFF_CAPS["features"] = int(_lib.load().am_rff_max_features())
-    return _RFF_CAPS["features"]
+    return _host_cap("am_rff_max_features")
 
 
 def rff_moment_chunks(n, n_features):
@@ -1880,12 +1646,8 @@ def _rff_width_args(bw2, inv_bw):
 
 
 def _rff_check_inputs(what, x, w):
-    if is_f64(x) or is_f64(w):
-        raise NotImplementedError(f"{what} takes float32 rows (the float64 matrix-core form is not implemented)")
-    if x.dim() != 2 or w.dim() != 2:
-        raise ValueError(f"rows and frequencies must be 2-D, got shapes {tuple(x.shape)} and {tuple(w.shape)}")
-    if x.shape[1] != w.shape[1]:
-        raise ValueError(f"feature widths differ: {x.shape[1]} and {w.shape[1]}")
+    _refuse_f64(what, x, w)
+    _check_two_sets(what, x, w, both="rows and frequencies", sides=False)
     if x.shape[0] < 1 or x.shape[1] < 1:
         raise ValueError(f"{what} needs rows (got shape {tuple(x.shape)})")
     if not 1 <= w.shape[0] <= rff_max_features():
@@ -1920,17 +1682,14 @@ def rff_features(x, w, bw2=None, inv_bw=None, row0=0, nrows=None, out=None, retu
     if out is not None and (not torch.is_tensor(out) or out.dtype != torch.float64 or out.dim() != 2 or out.shape[0] != 2 * r
                             or out.shape[1] < nrows or not out.is_contiguous()):
         raise ValueError(f"out must be a contiguous float64 [2R = {2 * r}, >= {nrows}] device tensor")
-    lib = _lib.load()
     x, w = as_matrix(x, "x"), as_matrix(w, "w")
     dev = _same_device(x, w) if out is None else _same_device(x, w, out)
     if bw2 is not None:
         _same_device(x, bw2)
     d = x.shape[1]
     f = torch.empty((2 * r, nrows), dtype=torch.float64, device=dev) if out is None else out
-    nb = lib.am_rff_features_workspace_bytes(nrows)
-    ws = _workspace(nb, dev)
-    _call(lib, "am_rff_features_f32", dev, _ptr(x), n_all, _ld(x), d, _ptr(w), r, _ld(w), row0, nrows, inv_arg, dev_arg, _ptr(f),
-          int(f.shape[1]), _ptr(ws), nb)
+    ws = _run("am_rff_features_f32", dev, "am_rff_features_workspace_bytes", (nrows,), _ptr(x), n_all, _ld(x), d, _ptr(w), r, _ld(w),
+              row0, nrows, inv_arg, dev_arg, _ptr(f), int(f.shape[1]))
     return (f, _rff_count_check(ws)) if return_check else f
 
 
@@ -1941,7 +1700,6 @@ def rff_moment(x, w, bw2=None, inv_bw=None):
     of rows with a NaN or an infinity (they count as zeros in s)."""
     _rff_check_inputs("rff_moment", x, w)
     inv_arg, dev_arg = _rff_width_args(bw2, inv_bw)
-    lib = _lib.load()
     x, w = as_matrix(x, "x"), as_matrix(w, "w")
     dev = _same_device(x, w)
     if bw2 is not None:
@@ -1949,9 +1707,8 @@ def rff_moment(x, w, bw2=None, inv_bw=None):
     n, d = x.shape
     r = int(w.shape[0])
     s = torch.empty((2 * r, 2 * r), dtype=torch.float64, device=dev)
-    nb = lib.am_rff_moment_workspace_bytes(n, d, r)
-    ws = _workspace(nb, dev)
-    _call(lib, "am_rff_moment_f32", dev, _ptr(x), n, _ld(x), d, _ptr(w), r, _ld(w), inv_arg, dev_arg, _ptr(s), _ptr(ws), nb)
+    ws = _run("am_rff_moment_f32", dev, "am_rff_moment_workspace_bytes", (n, d, r), _ptr(x), n, _ld(x), d, _ptr(w), r, _ld(w), inv_arg,
+              dev_arg, _ptr(s))
     return s, _rff_count_check(ws)
 
 
@@ -1984,19 +1741,14 @@ def class_group_scores(rows, order, offsets, return_rows=False):
     offs, b, host_offs = _group_offsets(offsets)
     if order is None and offs[-1] > rows.shape[0]:
         raise ValueError(f"no index list: offsets name {offs[-1]} stored rows, rows holds {rows.shape[0]}")
-    lib = _lib.load()
-    f64 = is_f64(rows)
-    rows = as_rows(rows, "rows")
+    rows, ld, kind = _rows(rows, "rows", is_f64(rows))
     n, c = rows.shape
     dev = rows.device
     idx = _group_index(order, offs[-1], rows)
     rec = torch.empty((b, 4), dtype=torch.float64, device=dev)
     h = torch.empty(offs[-1], dtype=torch.float64, device=dev) if return_rows else None
-    nb = lib.am_class_groups_workspace_bytes(offs[-1], b, c)
-    ws = _workspace(nb, dev)
-    _call(lib, "am_class_groups_f64" if f64 else "am_class_groups_f32", dev, _ptr(rows), n, _ld64(rows) if f64 else _ld(rows), c,
-          _ptr(idx) if idx is not None else ctypes.c_void_p(None), ctypes.cast(host_offs, ctypes.c_void_p), b, _ptr(rec),
-          _ptr(h) if h is not None else ctypes.c_void_p(None), _ptr(ws), nb)
+    ws = _run("am_class_groups_" + kind, dev, "am_class_groups_workspace_bytes", (offs[-1], b, c), _ptr(rows), n, ld, c, _opt(idx),
+              _host(host_offs), b, _ptr(rec), _opt(h))
     return rec, h, _index_check(ws, idx, n, "group rows")
 
 
@@ -2027,20 +1779,16 @@ def row_pair_scores(a, b, mode, eps=0.0, return_rows=False):
     values, or None unless return_rows.  Stream-ordered, nothing waits for the device; all arithmetic is f64 and every sum
     has a fixed order."""
     eps = check_row_pair(a, b, mode, eps)
-    lib = _lib.load()
     f64 = is_f64(a)
     same = a is b
-    a = as_rows(a, "a")
-    b = a if same else as_rows(b, "b")
+    a, lda, kind = _rows(a, "a", f64)
+    b, ldb = (a, lda) if same else _rows(b, "b", f64)[:2]
     dev = _same_device(a, b)
     n, c = a.shape
     sums = torch.empty(4, dtype=torch.float64, device=dev)
     rows = torch.empty(n, dtype=torch.float64, device=dev) if return_rows else None
-    nb = lib.am_row_pairs_workspace_bytes(n)
-    ws = _workspace(nb, dev)
-    ld = _ld64 if f64 else _ld
-    _call(lib, "am_row_pairs_f64" if f64 else "am_row_pairs_f32", dev, _ptr(a), ld(a), _ptr(b), ld(b), n, c, PAIR_MODES[mode], eps,
-          _ptr(rows) if rows is not None else ctypes.c_void_p(None), _ptr(sums), _ptr(ws), nb)
+    _run("am_row_pairs_" + kind, dev, "am_row_pairs_workspace_bytes", (n,), _ptr(a), lda, _ptr(b), ldb, n, c, PAIR_MODES[mode], eps,
+         _opt(rows), _ptr(sums))
     return sums, rows
 
 
@@ -2079,52 +1827,43 @@ def knn_sym_eligible(n, d, k, dtype=None):
 
 def knn_bounds(x_full, k, row0, nrows, prepared=None):
     """Squared upper bounds for rows [row0, row0+nrows) of the full set (column-sample pre-pass)."""
-    lib = _lib.load()
     x = as_matrix(x_full)
     n, d = x.shape
     out = torch.empty(int(nrows), dtype=torch.float32, device=x.device)
-    nb = lib.am_knn_part_workspace_bytes(n, d, int(k))
-    ws = _workspace(nb, x.device)
+    query, tail = ("am_knn_part_workspace_bytes", (n, d, int(k))), (int(k), int(row0), int(nrows), _ptr(out))
     if prepared is not None:
         ps = prepared.struct()
-        _call(lib, "am_knn_bounds_prepared_f32", x.device, _ptr(x), n, _ld(x), d, ctypes.byref(ps), int(k), int(row0), int(nrows),
-              _ptr(out), _ptr(ws), nb)
-        return out
-    _call(lib, "am_knn_bounds_f32", x.device, _ptr(x), n, _ld(x), d, int(k), int(row0), int(nrows), _ptr(out), _ptr(ws), nb)
+        _run("am_knn_bounds_prepared_f32", x.device, *query, _ptr(x), n, _ld(x), d, ctypes.byref(ps), *tail)
+    else:
+        _run("am_knn_bounds_f32", x.device, *query, _ptr(x), n, _ld(x), d, *tail)
     return out
 
 
 def knn_sym_part(x_full, k, part, nparts, bounds_sq, prepared=None):
     """This rank's share of the symmetric k-NN: [N, width] smallest entries per row (+inf padded)."""
-    lib = _lib.load()
     x = as_matrix(x_full)
     n, d = x.shape
-    width = lib.am_knn_list_width(int(k))
+    width = _lib.load().am_knn_list_width(int(k))
     bounds_sq = bounds_sq.to(torch.float32).contiguous().clone()
     out = torch.empty((n, width), dtype=torch.float32, device=x.device)
-    nb = lib.am_knn_part_workspace_bytes(n, d, int(k))
-    ws = _workspace(nb, x.device)
+    query, tail = ("am_knn_part_workspace_bytes", (n, d, int(k))), (int(k), int(part), int(nparts), _ptr(bounds_sq), _ptr(out))
     if prepared is not None:
         ps = prepared.struct()
-        _call(lib, "am_knn_sym_part_prepared_f32", x.device, _ptr(x), n, _ld(x), d, ctypes.byref(ps), int(k), int(part), int(nparts),
-              _ptr(bounds_sq), _ptr(out), _ptr(ws), nb)
-        return out
-    _call(lib, "am_knn_sym_part_f32", x.device, _ptr(x), n, _ld(x), d, int(k), int(part), int(nparts), _ptr(bounds_sq), _ptr(out),
-          _ptr(ws), nb)
+        _run("am_knn_sym_part_prepared_f32", x.device, *query, _ptr(x), n, _ld(x), d, ctypes.byref(ps), *tail)
+    else:
+        _run("am_knn_sym_part_f32", x.device, *query, _ptr(x), n, _ld(x), d, *tail)
     return out
 
 
 def knn_lists_finish(lists, x_full, k):
     """[nparts, N, width] per-rank lists -> radii f32[N] (bit-identical to knn_radii(x_full, k))."""
-    lib = _lib.load()
     x = as_matrix(x_full)
     n, d = x.shape
     lists = lists.to(torch.float32).contiguous()
     nparts = lists.shape[0]
     out = torch.empty(n, dtype=torch.float32, device=x.device)
-    nb = lib.am_knn_lists_finish_workspace_bytes(n, d, int(k))
-    ws = _workspace(nb, x.device)
-    _call(lib, "am_knn_lists_finish_f32", x.device, _ptr(lists), nparts, _ptr(x), n, _ld(x), d, int(k), _ptr(out), _ptr(ws), nb)
+    _run("am_knn_lists_finish_f32", x.device, "am_knn_lists_finish_workspace_bytes", (n, d, int(k)), _ptr(lists), nparts, _ptr(x), n,
+         _ld(x), d, int(k), _ptr(out))
     return out
 
 
@@ -2132,47 +1871,27 @@ def prdc_counts(ref, cand, r_ref, r_cand, want_min=False, prepared_ref=None, pre
     """col_count i32[Nc], row_any u8[Nr], row_cover u8[Nr] (prdc.py:34-48); with want_min=True also the row
     minimum f32[Nr] (not needed by any metric; costs extra).  float64 rows (either set): distances, radii and the comparisons
     in f64 (am_prdc_counts_f64; the row minimum is then f64 too)."""
-    lib = _lib.load()
     _require_cuda(r_ref, "r_ref")
     _require_cuda(r_cand, "r_cand")
-    if is_f64(ref) or is_f64(cand):
-        ref, cand = as_matrix64(ref, "reference"), as_matrix64(cand, "candidate")
-        r_ref, r_cand = r_ref.to(torch.float64).contiguous(), r_cand.to(torch.float64).contiguous()
-        nr, d = ref.shape
-        nc = cand.shape[0]
-        if r_ref.numel() != nr or r_cand.numel() != nc or cand.shape[1] != d:
-            raise ValueError("radius / embedding shapes do not match")
-        col = torch.empty(nc, dtype=torch.int32, device=ref.device)
-        rany = torch.empty(nr, dtype=torch.uint8, device=ref.device)
-        rcov = torch.empty(nr, dtype=torch.uint8, device=ref.device)
-        rmin = torch.empty(nr, dtype=torch.float64, device=ref.device) if want_min else None
-        nb = lib.am_prdc_f64_workspace_bytes(nr, nc, d)
-        ws = _workspace(nb, ref.device)
-        _call(lib, "am_prdc_counts_f64", ref.device, _ptr(ref), nr, _ld64(ref), _ptr(cand), nc, _ld64(cand), d, _ptr(r_ref), _ptr(r_cand),
-              _ptr(col), _ptr(rany), _ptr(rcov), _ptr(rmin) if want_min else ctypes.c_void_p(None), _ptr(ws), nb)
-        return (col, rany, rcov, rmin) if want_min else (col, rany, rcov)
-    ref, cand = as_matrix(ref, "reference"), as_matrix(cand, "candidate")
-    r_ref = r_ref.to(torch.float32).contiguous()
-    r_cand = r_cand.to(torch.float32).contiguous()
+    f64 = _any_f64(ref, cand)
+    (ref, ldr, kind), (cand, ldc, _) = _rows(ref, "reference", f64), _rows(cand, "candidate", f64)
+    r_ref, r_cand = r_ref.to(ref.dtype).contiguous(), r_cand.to(ref.dtype).contiguous()
     nr, d = ref.shape
     nc = cand.shape[0]
     if r_ref.numel() != nr or r_cand.numel() != nc or cand.shape[1] != d:
         raise ValueError("radius / embedding shapes do not match")
-    col = torch.empty(nc, dtype=torch.int32, device=ref.device)
-    rany = torch.empty(nr, dtype=torch.uint8, device=ref.device)
-    rcov = torch.empty(nr, dtype=torch.uint8, device=ref.device)
-    rmin = torch.empty(nr, dtype=torch.float32, device=ref.device) if want_min else None
-    nb = lib.am_prdc_workspace_bytes(nr, nc, d)
-    ws = _workspace(nb, ref.device)
-    if prepared_ref is not None and prepared_cand is not None:
+    dev = ref.device
+    col = torch.empty(nc, dtype=torch.int32, device=dev)
+    rany = torch.empty(nr, dtype=torch.uint8, device=dev)
+    rcov = torch.empty(nr, dtype=torch.uint8, device=dev)
+    rmin = torch.empty(nr, dtype=ref.dtype, device=dev) if want_min else None
+    query, tail = (_query("prdc", f64), (nr, nc, d)), (d, _ptr(r_ref), _ptr(r_cand), _ptr(col), _ptr(rany), _ptr(rcov), _opt(rmin))
+    if not f64 and prepared_ref is not None and prepared_cand is not None:
         pr, pc = prepared_ref.struct(), prepared_cand.struct()
-        _call(lib, "am_prdc_counts_prepared_f32", ref.device, _ptr(ref), nr, _ld(ref), ctypes.byref(pr), _ptr(cand), nc, _ld(cand),
-              ctypes.byref(pc), d, _ptr(r_ref), _ptr(r_cand), _ptr(col), _ptr(rany), _ptr(rcov),
-              _ptr(rmin) if want_min else ctypes.c_void_p(None), _ptr(ws), nb)
-        return (col, rany, rcov, rmin) if want_min else (col, rany, rcov)
-    _call(lib, "am_prdc_counts_f32", ref.device, _ptr(ref), nr, _ld(ref), _ptr(cand), nc, _ld(cand), d, _ptr(r_ref),
-                                      _ptr(r_cand), _ptr(col), _ptr(rany), _ptr(rcov),
-                                      _ptr(rmin) if want_min else ctypes.c_void_p(None), _ptr(ws), nb)
+        _run("am_prdc_counts_prepared_f32", dev, *query, _ptr(ref), nr, ldr, ctypes.byref(pr), _ptr(cand), nc, ldc, ctypes.byref(pc),
+             *tail)
+    else:
+        _run("am_prdc_counts_" + kind, dev, *query, _ptr(ref), nr, ldr, _ptr(cand), nc, ldc, *tail)
     return (col, rany, rcov, rmin) if want_min else (col, rany, rcov)
 
 
@@ -2220,6 +1939,16 @@ def release_workspaces(device=None):
         del _EVAL_WS[key]
 
 
+def _eval_request(what, idx_cand, idx_ref):
+    """The request half of both evaluate calls: (flags of `what`, the two KD index tables as the library takes them, S, m)."""
+    flags = sum(bit for name, bit in (("fad", EVAL_FAD), ("kd", EVAL_KD), ("prdc", EVAL_PRDC)) if name in what)
+    s = m = 0
+    if flags & EVAL_KD:
+        idx_cand, idx_ref = _index_table(idx_cand, "idx_cand"), _index_table(idx_ref, "idx_ref")
+        s, m = idx_cand.shape
+    return flags, idx_cand, idx_ref, s, m
+
+
 def evaluate(ref, cand, what, nearest_k=5, idx_cand=None, idx_ref=None, gamma=None, coef0=1.0, degree=3,
              given_ref=None, given_cand=None):
     """am_evaluate_f32: FAD / KD / PRDC of (candidate vs reference) as ONE stream-ordered chain with ONE read-back.
@@ -2235,11 +1964,7 @@ def evaluate(ref, cand, what, nearest_k=5, idx_cand=None, idx_ref=None, gamma=No
     n_cand = cand.shape[0]
     if cand.shape[1] != d:
         raise ValueError("feature dimensions differ")
-    flags = sum(bit for name, bit in (("fad", EVAL_FAD), ("kd", EVAL_KD), ("prdc", EVAL_PRDC)) if name in what)
-    s = m = 0
-    if flags & EVAL_KD:
-        idx_cand, idx_ref = _index_table(idx_cand, "idx_cand"), _index_table(idx_ref, "idx_ref")
-        s, m = idx_cand.shape
+    flags, idx_cand, idx_ref, s, m = _eval_request(what, idx_cand, idx_ref)
     keep = []
 
     def side(given, rows):
@@ -2275,9 +2000,7 @@ def evaluate(ref, cand, what, nearest_k=5, idx_cand=None, idx_ref=None, gamma=No
     s_ref, s_cand = side(given_ref, n_ref), side(given_cand, n_cand)
     with torch.cuda.device(dev):
         main = torch.cuda.current_stream(dev)
-        side_stream = _SIDE_STREAMS.get(("fad", dev.index))
-        if side_stream is None:
-            side_stream = _SIDE_STREAMS[("fad", dev.index)] = torch.cuda.Stream(dev)
+        side_stream = _side_stream(("fad", dev.index), dev)
         nb = lib.am_evaluate_workspace_bytes(n_ref, n_cand, d, int(nearest_k), s, m, flags)
         ws = _eval_workspace(nb, dev)
         out = torch.empty(EVAL_HEAD + s, dtype=torch.float64, device=dev)
@@ -2320,21 +2043,13 @@ def evaluate_sharded_c(ref_local, cand_local, ref_counts, cand_counts, what, col
     d = ref_local.shape[1]
     if cand_local.shape[1] != d or ref_local.shape[0] != ref_counts[rank] or cand_local.shape[0] != cand_counts[rank]:
         raise ValueError("the shards do not match the shard sizes / each other")
-    flags = sum(bit for name, bit in (("fad", EVAL_FAD), ("kd", EVAL_KD), ("prdc", EVAL_PRDC)) if name in what)
-    s = m = 0
-    if flags & EVAL_KD:
-        idx_cand, idx_ref = _index_table(idx_cand, "idx_cand"), _index_table(idx_ref, "idx_ref")
-        s, m = idx_cand.shape
+    flags, idx_cand, idx_ref, s, m = _eval_request(what, idx_cand, idx_ref)
     rc_arr = (ctypes.c_int64 * world)(*ref_counts)
     cc_arr = (ctypes.c_int64 * world)(*cand_counts)
     with torch.cuda.device(dev):
         main = torch.cuda.current_stream(dev)
-        side_stream = _SIDE_STREAMS.get(("fad", dev.index))
-        if side_stream is None:
-            side_stream = _SIDE_STREAMS[("fad", dev.index)] = torch.cuda.Stream(dev)
-        comm_stream = _SIDE_STREAMS.get(("comm", dev.index))
-        if comm_stream is None:
-            comm_stream = _SIDE_STREAMS[("comm", dev.index)] = torch.cuda.Stream(dev)
+        side_stream = _side_stream(("fad", dev.index), dev)
+        comm_stream = _side_stream(("comm", dev.index), dev)
         nb = lib.am_evaluate_sharded_workspace_bytes(rc_arr, cc_arr, rank, world, d, int(nearest_k), s, m, flags)
         if nb == 0:
             raise ValueError(f"empty embedding set: {sum(ref_counts)} reference and {sum(cand_counts)} candidate rows over {world} ranks")
